@@ -1,6 +1,7 @@
 """Benchmark: log_prob throughput of the gfx950 flow-transform hot path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5f|cfg5i|...]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 `--gpus N` with no launcher around it (WORLD_SIZE unset) starts the N ranks itself as child
@@ -24,14 +25,18 @@ leaves less idle between steps than a graph replay (measured, `profiles/r05_grap
 cfg2 125k 164.7 vs 167.0 us, cfg3 125k 131.9 vs 136.0 us, cfg5i 1Ki 32.1 vs 36.3 us, cfg2 1M
 equal). The sample4k* steps (several small launches each) keep the graph (`--eager` opts out).
 
-At the default config (cfg2, RealNVP d=2) the line nests the second half of the metric, MAF
-d=63 (cfg4, 5x MAF(63,64), 4M samples split over the ranks), with its own roofline and CPU
-baseline under "maf_d63".
+A plain run sets up, warms up, times the K steps and rank 0 prints ONE JSON line with the
+throughput, `ms_per_step` and the NLL of the last timed step against the reference's stored one
+(read off that step's output, no pass of its own). `--dump-outputs DIR` also writes what the last
+timed step returned (log p and its sums; samples and log-dets; the loss and the stepped weights)
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
-Rank 0 prints ONE JSON line with the throughput, the roofline of the dominant kernel (HIP
-events on the launch stream, over the timed steps) and, at N=1, the oracle CPU baseline timed on
-this host (threads = physical cores within this process's CPU allotment) on a bounded sample of
-the same workload.
+`--full` adds everything that takes runs of its own: the roofline of the dominant kernel (HIP
+events on the launch stream, the K steps again), at N=1 the oracle CPU baseline timed on this
+host (threads = physical cores within this process's CPU allotment) on a bounded sample of the
+same workload, the sampling configs' checksums against the reference, and at the default config
+(cfg2, RealNVP d=2) the second half of the metric nested under "maf_d63": MAF d=63 (cfg4, 5x
+MAF(63,64), 4M samples split over the ranks) with its own roofline and CPU baseline.
 """
 import argparse
 import glob
@@ -414,8 +419,35 @@ def cpu_training_baseline(model, spec, x_gpu, budget_s=12.0, max_rows=32768):
 CPU_ROWS = {"cfg2": 1_000_000, "cfg3": 1_000_000, "cfg4": 1_000_000, "cfg5f": 16_384, "cfg5i": 1_024}
 
 
-def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
-    """One benchmark line (dict on rank 0, None elsewhere)."""
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all arrays of one run together stay under 64 MB
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """--dump-outputs: write `arrays` ({name: tensor}) as DIR/<name>.npy (rank r > 0 of a multi-GPU
+    run: DIR/<name>.rank<r>.npy), float64 tensors as float64 and everything else as float32. The
+    byte budget is split evenly over the arrays; one that exceeds its share is cut to a fixed,
+    seeded sample of its rows (sorted, the same rows in every run of the same shape)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+        if t.dim() == 0:
+            t = t.reshape(1)
+        rows = t.shape[0]
+        keep = max(1, share // max(1, t[0].numel() * t.element_size())) if rows else 0
+        if rows > keep:
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(20231))[:keep].sort().values
+            t = t.index_select(0, idx.to(t.device))
+        suffix = "" if rank == 0 else f".rank{rank}"
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), t.cpu().numpy())
+
+
+def run_config(config, a, world, rank, dev, strong, graph, with_cpu, full=True, dump_dir=None):
+    """One benchmark line (dict on rank 0, None elsewhere). `full` adds what takes runs of its own
+    beyond the timed steps: the per-kernel event pass behind the roofline, the CPU baseline, the
+    sampling configs' checksum pass. `dump_dir`: write the last timed step's outputs there."""
     model, d, f_layer, spec, desc = build(config)
     training = config in TRAIN_CONFIGS
     coupling_train = config in ("cfg2t", "train5k", "trainfig")
@@ -489,6 +521,8 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
             w.wait()
         pending.clear()
 
+    last_logp = [None]  # the eager log_prob step returns only the sums: --dump-outputs wants log p too
+
     def step():
         if graphed_train is not None and not eager_only[0]:
             loss = graphed_train()
@@ -509,13 +543,14 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
             out = graphed()
             if sampling:
                 return out
-            sums = out[1]
+            last_logp[0], sums = out[0], out[1]
         elif sampling and fused_draw:  # z ~ N(0, I) drawn inside the chain kernel, x = forward(z)
             return flow.sample_fused(B, dev)
         elif sampling:  # sampling pass: x = forward(z), no exchange
             return flow.forward(x)
         else:
             logp, sums = flow.log_prob(x, return_sums=True)
+            last_logp[0] = logp
         if world > 1:
             sums = sums.clone()
             pending.append(dist.all_reduce(sums, async_op=True))  # RCCL over xGMI: 16 bytes
@@ -544,6 +579,20 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
         w1 = time.monotonic_ns()
         torch_calls = nfs_amd.STATS["torch"]
         hip_calls = nfs_amd.STATS["hip"]
+    if dump_dir:
+        # what a caller of the timed path received from its last step (before any further pass
+        # moves the weights of a training config)
+        if training:
+            arrays = {"loss": -out[0] / out[1]}
+            arrays.update({"param." + k: v for k, v in model.state_dict().items() if v.is_floating_point()})
+        elif sampling:
+            outs = (out,) if torch.is_tensor(out) else tuple(out)
+            arrays = dict(zip(("samples", "log_det", "z"), outs))  # the eager fused draw returns its z too
+        else:
+            arrays = {"log_prob": last_logp[0], "log_prob_sums": out}
+        dump_outputs(dump_dir, arrays, rank)
+
+    def event_pass():
         # Kernel durations: the same K steps again with HIP events around every layer launch
         # on the launch stream. Kept out of the headline loop because each event record adds
         # ~5 us of GPU idle between kernels (measured, profiles/).
@@ -602,6 +651,12 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
             torch.cuda.synchronize()
             events = rec
             flow.layer_events = None
+        return events, aux_events
+
+    events, aux_events = [], []
+    if full:
+        with torch.set_grad_enabled(training):
+            events, aux_events = event_pass()
     if torch_calls != 0 or (hip_calls == 0 and graphed is None and graphed_train is None):
         raise RuntimeError(f"hot path did not run on the HIP kernels: {nfs_amd.STATS}")
     t_all = torch.tensor([t], device=dev, dtype=torch.float64)
@@ -623,7 +678,8 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
     # library as dispatched (nfx_last_kernel)
     durs = [e0.elapsed_time(e1) for _, e0, e1 in events]
     kname = events[0][0] if events else "?"
-    mean_ms = sum(durs) / max(1, len(durs))
+    # (a plain run has no event pass: the roofline figures below come out NaN and the line drops them)
+    mean_ms = sum(durs) / len(durs) if durs else float("nan")
     # one-launch coupling chains (nfx_affine_chain / nfx_spline_chain): one event covers every layer
     layers_per_launch = len(flow.flows) if kname in ("affine_chain_kernel", "affine_schain_kernel",
                                                      "spline_chain_kernel", "spline_schain_kernel") else 1
@@ -633,7 +689,7 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
     # result vs the reference's own full-scale run (global over ranks)
     ref_check = None
     nll = None
-    if sampling and x_ref is not None:
+    if sampling and x_ref is not None and full:  # a forward pass of its own
         with torch.no_grad():
             xo, ldo = flow.forward(x)
             cs = torch.stack([xo.double().sum(), xo.double().abs().sum(), ldo.double().sum()])
@@ -647,6 +703,7 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
                      "ld_mean_abs_diff": abs(cs[2] - meta["ld_sum_f64"]) / meta["B"],
                      "source": "tests/golden/g8_full_nll.json " + REFERENCE_RUN[config]["g8"]}
     elif not sampling and not training:
+        # read off the last timed step's own output (no further pass): stays in a plain run
         sums = out  # the last timed step's [sum log p, count], all-reduced over the ranks
         nll = -float(sums[0] / sums[1])
         if x_ref is not None:
@@ -668,7 +725,7 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
     tp = os.path.join(ROOT, "profiles", f"rocprof_{rp_name}.json")
     lib_sha = lib_digest()
     rj = None
-    if os.path.exists(tp):
+    if full and os.path.exists(tp):
         with open(tp) as fh:
             rj = json.load(fh)
     if rj is not None and rj.get("lib_sha256") != lib_sha:
@@ -835,6 +892,10 @@ def run_config(config, a, world, rank, dev, strong, graph, with_cpu):
                                            "bytes_per_launch": fac_bytes,
                                            "achieved": fac_bytes / (wms * 1e-3) / 1e9, "peak": 8000.0,
                                            "unit": "GB/s", "frac": fac_bytes / (wms * 1e-3) / 1e9 / 8000.0}
+    result["full"] = full
+    if not full:
+        result["roofline"] = None  # its figures need the event pass
+        return result
     if world == 1 and with_cpu and training:
         result["cpu_baseline"] = cpu_training_baseline(model, spec, x)
     elif world == 1 and with_cpu:
@@ -973,7 +1034,15 @@ def main(argv=None):
                     help="sample4k* configs: eager launches instead of the captured HIP graph (GraphedFlow)")
     ap.add_argument("--weak", action="store_true", help="weak scaling: every rank processes the whole batch")
     ap.add_argument("--strong", action="store_true", help="(default) strong scaling: split the batch over the ranks")
-    ap.add_argument("--no-secondary", action="store_true", help="cfg2: skip the nested MAF d=63 (cfg4) line")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="--full at cfg2: skip the nested MAF d=63 (cfg4) line")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the timed steps, also measure what takes runs of its own: the per-kernel event pass "
+                         "and roofline, the CPU baseline (--no-cpu skips it), the sampling configs' checksum pass and, "
+                         "at cfg2, the nested MAF d=63 line (--no-secondary skips it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32 or "
+                         "float64, under 64 MB in all: a fixed seeded sample of the rows of a larger array)")
     a = ap.parse_args(argv)
     if a.gpus < 1:
         raise SystemExit(f"--gpus must be >= 1 (got {a.gpus})")
@@ -1015,9 +1084,10 @@ def main(argv=None):
     training = a.config in TRAIN_CONFIGS
     graph = a.graph if training else ((not a.eager) if a.config.startswith("sample4k") else (a.graph and not a.eager))
     strong = not a.weak
-    result = run_config(a.config, a, world, rank, dev, strong, graph, not a.no_cpu)
-    if a.config == "cfg2" and not a.no_secondary:
-        sec = run_config("cfg4", a, world, rank, dev, strong, graph, not a.no_cpu)
+    with_cpu = a.full and not a.no_cpu
+    result = run_config(a.config, a, world, rank, dev, strong, graph, with_cpu, a.full, a.dump_outputs)
+    if a.full and a.config == "cfg2" and not a.no_secondary:
+        sec = run_config("cfg4", a, world, rank, dev, strong, graph, with_cpu)
         if rank == 0:
             result["maf_d63"] = sec
     if rank == 0:

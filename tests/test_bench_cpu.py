@@ -61,6 +61,31 @@ def test_gpus_flag_rank_failure_fails_the_run():
     assert "rank 1 exited" in r.stderr
 
 
+def test_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else is written as float32, an array over
+    its share of the byte budget is cut to the same seeded rows every time, all files < 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    big = torch.randn(bench.DUMP_BUDGET_BYTES // 32, 8, generator=g)  # 3x its third of the budget
+    big[:, 0] = torch.arange(big.shape[0])  # (exact in fp32) each row carries its own index
+    arrays = {"log_prob": big, "sums": torch.tensor([1.5, 2.0], dtype=torch.float64), "loss": torch.tensor(0.25).half()}
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), arrays)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["log_prob.npy", "loss.npy", "sums.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 64_000_000
+    a, b = (np.load(tmp_path / s / "log_prob.npy") for s in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_BUDGET_BYTES // 3 // 32, 8) and np.array_equal(a, b)
+    idx = a[:, 0].astype(np.int64)
+    assert (np.diff(idx) > 0).all() and np.array_equal(a, big.numpy()[idx])  # rows of the array itself, in order
+    s = np.load(tmp_path / "a" / "sums.npy")
+    assert s.dtype == np.float64 and s.tolist() == [1.5, 2.0]
+    lo = np.load(tmp_path / "a" / "loss.npy")
+    assert lo.dtype == np.float32 and lo.tolist() == [0.25]
+
+
 def test_world_size_must_match_gpus():
     r = _bench({"WORLD_SIZE": "3", "RANK": "0", "LOCAL_RANK": "0"}, "--gpus", "2")
     assert r.returncode != 0 and "must agree" in r.stderr

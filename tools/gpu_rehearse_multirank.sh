@@ -7,6 +7,6 @@ cd $R
 export NFX_BENCH_REHEARSE=1
 for c in cfg2 cfg4t cfg5i; do
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-    --master-port 29511 bench.py --gpus 2 --config $c --steps 5 --warmup 2 --no-cpu > $O/r2_$c.json 2> $O/r2_$c.err || exit $?
+    --master-port 29511 bench.py --gpus 2 --config $c --full --steps 5 --warmup 2 --no-cpu > $O/r2_$c.json 2> $O/r2_$c.err || exit $?
   echo "rehearsed $c"
 done

@@ -28,19 +28,19 @@ for spec0 in "$@"; do
   rm -rf "$d"
   mkdir -p "$d"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$d/trace" -- \
-    python3 "$root/bench.py" --config "$c" "${extra[@]}" --steps 20 --warmup 5 --no-cpu --no-secondary \
+    python3 "$root/bench.py" --config "$c" "${extra[@]}" --full --steps 20 --warmup 5 --no-cpu --no-secondary \
     > "$d/bench.json" 2> "$d/trace.err" || exit $?
   if [ "$pmc" = 1 ]; then
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$d/fetch" -- \
-      python3 "$root/bench.py" --config "$c" "${extra[@]}" --steps 3 --warmup 1 --no-cpu --no-secondary \
+      python3 "$root/bench.py" --config "$c" "${extra[@]}" --full --steps 3 --warmup 1 --no-cpu --no-secondary \
       > "$d/fetch.log" 2>&1 || exit $?
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$d/write" -- \
-      python3 "$root/bench.py" --config "$c" "${extra[@]}" --steps 3 --warmup 1 --no-cpu --no-secondary \
+      python3 "$root/bench.py" --config "$c" "${extra[@]}" --full --steps 3 --warmup 1 --no-cpu --no-secondary \
       > "$d/write.log" 2>&1 || exit $?
     # MFMA pipe busy cycles, instruction mix and the clock (GRBM_GUI_ACTIVE over the 8 XCDs)
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE \
       --output-format csv -d "$d/mfma" -- \
-      python3 "$root/bench.py" --config "$c" "${extra[@]}" --steps 3 --warmup 1 --no-cpu --no-secondary \
+      python3 "$root/bench.py" --config "$c" "${extra[@]}" --full --steps 3 --warmup 1 --no-cpu --no-secondary \
       > "$d/mfma.log" 2>&1 || exit $?
   fi
   echo "profiled $name"
