@@ -83,16 +83,16 @@ __global__ void affine_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const float
 
 // The split tail of an affine image (affine_split, nfx_affine_kernel.h), derived from the fp32
 // image written before it on the same stream: copies of w1 b1 b2 w3 b3 and the mask, W2's three
-// round-to-nearest bf16 pieces in v_mfma_f32_32x32x16_bf16 A-operand order, and the safety words (W2 finite
-// and |w| <= 1e6; xsafe = (1e30 - max|b1|) / max_row sum|w1|). One workgroup: the two maxima
-// are reductions and the tail is ~14k floats.
+// round-to-nearest bf16 pieces in v_mfma_f32_32x32x16_bf16 A-operand order, and the safety words (W2 finite,
+// |w| <= 1e6 and the lower-edge bound below; xsafe = (1e30 - max|b1|) / max_row sum|w1|). One
+// workgroup: the maxima are reductions and the tail is ~14k floats.
 __global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, int d, int H) {
     const int HT = (H + 31) / 32, KS1 = (d + 1) / 2;
     const AffineLayout L = affine_layout(d, HT);
     const AffineSplit S = affine_split(d, HT);
     float* out = packed + L.s;
     __shared__ int w2_bad;
-    __shared__ float rowsum[2 * 64], bmax[2 * 64];
+    __shared__ float rowsum[2 * 64], bmax[2 * 64], w2sum[2 * 64], w3sum[2 * 8];
     if (threadIdx.x == 0) w2_bad = 0;
     __syncthreads();
     bool bad = false;
@@ -137,10 +137,13 @@ __global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, 
         out[i] = __uint_as_float(v);
     }
     if (bad) atomicOr(&w2_bad, 1);
-    // layer-1 bound: row sums of |w1| (rows 32 ht + c of net n) and |b1|
+    // layer-1 bound: row sums of |w1| (rows 32 ht + c of net n) and |b1|; for the lower edge
+    // below: the row sums of |w2| (same rows) and of |w3| (output j of net n)
     for (int i = threadIdx.x; i < 2 * 64; i += blockDim.x) {
         rowsum[i] = 0.f;
         bmax[i] = 0.f;
+        w2sum[i] = 0.f;
+        if (i < 2 * 8) w3sum[i] = 0.f;
     }
     __syncthreads();
     if (threadIdx.x < 2 * 32 * HT) {
@@ -155,6 +158,18 @@ __global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, 
             for (int hh = 0; hh < 2; ++hh)
                 if (crow(r, hh) == c) b = fabsf(P[L.b1 + ht * 32 + 16 * hh + r]);
         bmax[net * 64 + row] = b;
+        float s2 = 0.f;  // row 32 ht + c of w2: lanes c and c + 32 of every (k tile, register) group
+        for (int g = 0; g < HT * 4; ++g)
+            for (int hh = 0; hh < 2; ++hh)
+                for (int rr = 0; rr < 4; ++rr) s2 += fabsf(P[L.w2 + (ht * HT * 4 + g) * 256 + (c + 32 * hh) * 4 + rr]);
+        w2sum[net * 64 + row] = s2;
+    }
+    if (threadIdx.x < 2 * d) {
+        const int net = threadIdx.x / d, j = threadIdx.x % d;
+        const float* P = packed + net * L.net;
+        float s3 = 0.f;
+        for (int t = 0; t < HT * 32; ++t) s3 += fabsf(P[L.w3 + j * HT * 32 + t]);
+        w3sum[net * 8 + j] = s3;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -166,7 +181,19 @@ __global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, 
             c1 = fmaxf(c1, bmax[i]);
         }
         const float xs = nan ? 0.f : (1e30f - c1) / n1;  // n1 == 0: +inf (no x reaches layer 1)
-        out[S.ok] = w2_bad ? 0.f : 1.f;
+        // Lower edge: split3's pieces go to the MFMA as bf16, whose smallest subnormal is 2^-133, so
+        // an activation below 2^-110 loses the bits of its third piece under 2^-133 (pack_bf16 cuts
+        // them). That moves a layer-2 output by less than 2^-133 * row-sum|w2| and s by that times
+        // row-sum|w3|: the layer stays on the split only while this stays under 2^-24, the
+        // relative rounding of exp(s) in fp32 (NaN or inf sums fail the test).
+        bool lost = false;
+        for (int net = 0; net < 2; ++net) {
+            float r2 = 0.f, r3 = 0.f;
+            for (int i = 0; i < 64; ++i) r2 = fmaxf(r2, w2sum[net * 64 + i]);
+            for (int j = 0; j < 8; ++j) r3 = fmaxf(r3, w3sum[net * 8 + j]);
+            lost = lost || !(0x1p-133 * (double)r2 * (double)r3 < 0x1p-24);
+        }
+        out[S.ok] = (w2_bad || lost) ? 0.f : 1.f;
         out[S.ok + 1] = xs > 0.f ? xs : 0.f;
         out[S.ok + 2] = 0.f;
         out[S.ok + 3] = 0.f;

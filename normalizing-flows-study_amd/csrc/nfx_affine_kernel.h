@@ -29,9 +29,10 @@ struct AffineLayout {
 // this region into LDS. Per net: w1 b1 b2 w3 b3 (copies, the fp32 formats above) and W2 as three
 // bf16 pieces W2 ~ W2_0 + W2_1 + W2_2 (round-to-nearest split, split_block) in v_mfma_f32_32x32x16_bf16
 // A-operand order [out tile][k block][piece][lane][4 dwords]; then the mask and two safety words:
-// ok[0] = 1 when every W2 entry is finite with |w| <= 1e6, ok[1] = xsafe, the largest |x * m|
-// for which every layer-1 activation stays <= 1e30 (so no bf16 piece product or layer-2 partial
-// sum can overflow).
+// ok[0] = 1 when every W2 entry is finite with |w| <= 1e6 and the activation bits cut below the
+// smallest bf16 subnormal cannot move s by 2^-24 (2^-133 * max row-sum|w2| * max row-sum|w3| <
+// 2^-24), ok[1] = xsafe, the largest |x * m| for which every layer-1 activation stays <= 1e30 (so
+// no bf16 piece product or layer-2 partial sum can overflow).
 struct AffineSplit {
     int w1, b1, b2, w3, b3, w2s, net, mask, ok, total;
 };
@@ -187,7 +188,8 @@ __device__ __forceinline__ void affine_net(const float* __restrict__ P, const Af
 // 4e-8, this split 1e-9, profiles/r06_split/). Six 32-cycle
 // MFMAs replace the eight 64-cycle fp32 MFMAs of a 16-deep k block, and the splitting VALU issues
 // in their shadow. A 32-row sample tile whose masked input fails |x * m| <= xsafe (non-finite or
-// huge), or a layer whose W2 is not finite / exceeds 1e6, runs the fp32 chain instead, so
+// huge), or a layer whose W2 is not finite / exceeds 1e6 / is so large next to W3 that the bits
+// cut from sub-2^-110 activations could show in s (ok[0]), runs the fp32 chain instead, so
 // non-finite rows keep the reference's inf / NaN propagation; the decision is per 32-row tile
 // (32-aligned in every kernel), so a row's bits depend only on its own tile.
 #ifndef NFX_SPLIT_TERMS
@@ -201,8 +203,13 @@ __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
                                                     0, 0, 0);
 }
 
-// The three pieces (fp32 bit patterns, zero low halves) of a finite activation x, by truncation:
-// x0 keeps x's top 8 significant bits, x1 the next 8 of the exact remainder, x2 the rest (exact).
+// The three pieces (fp32 bit patterns) of a finite activation x, by truncation: x0 keeps x's top 8
+// significant bits, x1 the next 8 of the exact remainder, u2 is the whole second remainder.
+// pack_bf16 keeps the top 16 bits of each pattern, so x2 is exact only AFTER that truncation and
+// only for |x| >= 2^-110: there the second remainder has at most 8 significant bits, all at or
+// above 2^-133, the smallest bf16 subnormal. Below 2^-110 its bits under 2^-133 are cut (each
+// activation then loses less than 2^-133 absolute); the pack's ok[0] bounds what that can do to s
+// (affine_split_pack_kernel, the lower edge).
 __device__ __forceinline__ void split3(float x, uint32_t& u0, uint32_t& u1, uint32_t& u2) {
     u0 = __float_as_uint(x) & 0xffff0000u;
     const float r1 = x - __uint_as_float(u0);

@@ -306,18 +306,29 @@ def test_split_mfma_fallback_is_per_tile(cuda_device):
     """A 32-row tile holding a non-finite or huge masked input runs the fp32 nets (the reference's
     inf / NaN propagation); the choice is per 32-aligned tile, so every other tile's rows — the
     other tile of the same 64-row unit included — are bit-identical to a clean batch, and the
-    tile's finite rows stay within the oracle's tolerance."""
+    tile's finite rows stay within the oracle's tolerance. Both bad values sit in the masked-in
+    column (layer 0's mask is [1, 0]: the kernel tests x * m), and both tiles are shown to have
+    left the split: their clean rows differ from the clean batch in at least one bit, and tile 3's
+    (huge but finite input) carry the bits of the run with inf in that element."""
     m, _ = realnvp_from_golden(cuda_device)
     layer = m.flow.flows[0]
+    assert layer.mask.tolist() == [1.0, 0.0]
     B = 1 << 17
     x = torch.randn(B, 2, generator=torch.Generator().manual_seed(7)).to(cuda_device)
     xb = x.clone()
     xb[40, 0] = float("inf")   # tile 1 (rows 32..63) of unit 0
-    xb[100, 1] = 3e38          # tile 3 (rows 96..127), huge but finite
+    xb[100, 0] = 3e38          # tile 3 (rows 96..127), huge but finite
+    xc = xb.clone()
+    xc[100, 0] = float("inf")
     L = nfs_amd._lib
     for fn in (layer.forward, layer.inverse):
         y0, l0 = _policy_run(L.NFX_AFFINE_STREAMING, lambda: fn(x))
         y1, l1 = _policy_run(L.NFX_AFFINE_STREAMING, lambda: fn(xb))
+        y2, l2 = _policy_run(L.NFX_AFFINE_STREAMING, lambda: fn(xc))
+        for lo, bad in ((32, 40), (96, 100)):
+            rows = [r for r in range(lo, lo + 32) if r != bad]
+            assert not (torch.equal(y0[rows], y1[rows]) and torch.equal(l0[rows], l1[rows])), f"tile at {lo} did not fall back"
+            assert torch.equal(y1[rows], y2[rows]) and torch.equal(l1[rows], l2[rows])
         keep = torch.ones(B, dtype=torch.bool, device=cuda_device)
         keep[32:64] = False
         keep[96:128] = False
