@@ -139,9 +139,9 @@ int nfx_affine_chain_logprob(const float* const* packs, int n_layers, const floa
  * reference's throughput loop plots/_common.py:264-274): z ~ N(0, I) drawn on the device
  * (Philox4x32-10 keyed by `seed`, counter = (sample, offset); Box-Muller), then the forward chain,
  * in ONE launch of the small-batch chain (B up to 64k rows at d = 2; NFX_EUNSUPPORTED above).
- * rng_state: device uint64[2] = {counter offset, arrival count}, zero-filled once; every launch
- * reads the offset and its last workgroup advances it, so repeated launches (and replays of a
- * captured graph) draw fresh values. z (may be NULL) receives the draws, x = forward(z) bit for bit
+ * rng_state: device uint64[2] = {counter offset, arrival word} as nfx_base_normal's (any content
+ * of the arrival word is valid); every launch reads the offset and its last workgroup advances it,
+ * so repeated launches (and replays of a captured graph) draw fresh values. z (may be NULL) receives the draws, x = forward(z) bit for bit
  * as nfx_affine_chain would give for that z, log_det written. */
 int nfx_affine_chain_sample(const float* const* packs, int n_layers, uint64_t seed, uint64_t* rng_state,
                             float* z, float* x, float* log_det, int64_t B, int d, int H, void* stream);
@@ -227,6 +227,19 @@ int nfx_arqs(const float* packed, const float* in, float* out, float* log_det, i
              void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The N(0, I) base draw on the device, for any shape: z[B, d] row-major, B >= 0, d >= 1.
+ * z[row, dim] is a pure function of (seed, offset, row, dim): Philox4x32-10 keyed by `seed`, counter
+ * (row, dim / 4, offset), Box-Muller on the word pairs (0, 1) and (2, 3) — the draw
+ * nfx_affine_chain_sample, nfx_spline_chain_sample and nfx_made_affine_sample fuse into their
+ * kernels, bit for bit. rng_state: device uint64[2] = {offset, arrival word}; [1] may hold anything
+ * on entry (zeros included: a word without the launch tag is claimed, as the log_prob workspace's),
+ * [0] is the offset the launch draws at, and its last workgroup adds 1 to it, so repeated launches
+ * and replays of a captured graph draw fresh values. Launches sharing one rng_state must be
+ * stream-ordered. B == 0 launches nothing and leaves the state as it is.
+ * ------------------------------------------------------------------------------------- */
+int nfx_base_normal(uint64_t seed, uint64_t* rng_state, float* z, int64_t B, int d, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * MADE-masked autoregressive affine flows — MADE (src/flows/autoregressive/made.py:6-140),
  * MaskedLinear (masked_linear.py:4-18), MaskedAutoregressiveFlow
  * (masked_autoregressive_flow.py:18-78), InverseAutoregressiveFlow
@@ -267,6 +280,16 @@ int nfx_made_seq_policy(int policy);
 int nfx_made_affine_logprob(const float* packed, const float* in, float* out, float* log_det,
                             float* logp, double* sums, void* workspace, int64_t B, int d, int H,
                             int variant, int accumulate, void* stream);
+/* The first layer of an IAF sampling stack with the base draw fused in: z ~ N(0, I) drawn in the
+ * tile kernel (the draw of nfx_base_normal at the same seed and state, bit for bit), x and log_det
+ * = nfx_made_affine(packed, z, ..., NFX_IAF_FORWARD, accumulate = 0) bit for bit, ONE launch. z and
+ * x must not alias. rng_state as nfx_base_normal. nfx_made_sample_supported: 1 exactly for the
+ * shapes and variant nfx_made_affine runs in that tile kernel (NFX_IAF_FORWARD, d <= 64, H <= 128);
+ * NFX_EUNSUPPORTED from nfx_made_affine_sample elsewhere (draw with nfx_base_normal, then
+ * nfx_made_affine). Host-only check. */
+int nfx_made_sample_supported(int d, int H, int variant);
+int nfx_made_affine_sample(const float* packed, uint64_t seed, uint64_t* rng_state, float* z, float* x,
+                           float* log_det, int64_t B, int d, int H, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Training: backward of the PARALLEL MADE directions under autograd —

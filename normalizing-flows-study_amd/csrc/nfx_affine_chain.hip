@@ -19,9 +19,9 @@
 namespace nfx {
 
 // SAMPLE (forward chains): the rows are not read from `in` but drawn on the device — z ~ N(0, I)
-// from Philox4x32-10 keyed by `seed` at the counter offset rng[0] (base_draw, nfx_chain.h),
+// from Philox4x32-10 keyed by `seed` at the counter offset rng[0] (base_draw, nfx_rng.h),
 // written to `zout` when non-null — and the LAST workgroup to finish advances rng[0] past this
-// launch's draws (arrival count in rng[1]), so a replayed graph draws fresh values every time.
+// launch's draws (rng_commit: tagged arrival word in rng[1]), so a replayed graph draws fresh values every time.
 template <int HT, int D, int DIR, bool LOGP, bool SAMPLE = false>
 __global__ __launch_bounds__(128 * HT) void affine_chain_kernel(NfxChainPacks packs, int nl, const float* __restrict__ in,
                                                                 float* __restrict__ out, float* __restrict__ logdet,
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(128 * HT) void affine_chain_kernel(NfxChainPacks pa
     const int nt = (int)(ntiles - t0 < tpw ? ntiles - t0 : tpw);
     const int64_t r0 = t0 * 32;
     if constexpr (SAMPLE) {
-        const uint64_t off = __hip_atomic_load(rng, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint64_t off = rng_offset(rng);
         for (int e = threadIdx.x; e < nt * 32; e += NTHR) {
             const int64_t row = r0 + e;
             float z[D];
@@ -196,19 +196,7 @@ __global__ __launch_bounds__(128 * HT) void affine_chain_kernel(NfxChainPacks pa
         logp_commit<NTHR>(lpacc, partials, sums, B);
     }
     if constexpr (SAMPLE) {
-        // every workgroup read rng[0] in its prologue; the last one to get here moves it on
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            uint64_t* cnt = rng + 1;
-            const uint64_t prev = __hip_atomic_fetch_add(cnt, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == (uint64_t)gridDim.x - 1) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                __hip_atomic_store(rng, __hip_atomic_load(rng, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(cnt, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
+        rng_commit(rng);  // every workgroup read rng[0] in its prologue; the last one here moves it on
     }
 }
 

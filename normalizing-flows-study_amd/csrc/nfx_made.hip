@@ -308,6 +308,31 @@ namespace nfx {
 int made_seq_policy_get() { return made_seq_policy().load(std::memory_order_relaxed); }
 }  // namespace nfx
 
+// made_tile_kernel's shapes: the parallel directions with d <= kTileMaxD, HT <= 4 (made_launch
+// and nfx_made_sample_supported both ask here).
+static bool tile_path(int d, int HT, int variant) {
+    return (variant == NFX_MAF_INVERSE || variant == NFX_IAF_FORWARD) && d > 0 && d <= kTileMaxD && HT >= 1 && HT <= 4;
+}
+
+// made_tile_kernel's launch shape. 8 waves per workgroup (two per SIMD) while the batch fills the
+// chip. Below that (no fused log_prob) as few waves per workgroup as spread the tiles one wave
+// per SIMD, the weights read through L2 rather than staged per workgroup: 6x IAF(2, 64) sampling
+// at n = 4,000 112 -> 73 us; staging the weights per workgroup measured no better at d = 63
+// (profiles/r06_tile/)
+struct TileConfig {
+    int nw;      // waves per workgroup
+    bool wlds;   // weights staged in LDS
+    size_t lds;  // dynamic LDS bytes
+};
+static TileConfig tile_config(const MadeLayout& L, int64_t ntiles, bool fused) {
+    int nw = 8;
+    if (!fused && ntiles < 4 * (int64_t)num_cus()) nw = (int)((ntiles + num_cus() - 1) / num_cus());
+    const size_t wbytes = (size_t)L.par_total * sizeof(float);
+    const size_t tiles = nw * 32 * (size_t)kTileStride * sizeof(float);
+    const bool wlds = nw == 8 && wbytes + tiles <= kLdsBytes;
+    return {nw, wlds, (wlds ? wbytes : 0) + tiles};
+}
+
 static int made_launch(const float* packed, const float* in, float* out, float* log_det, int64_t B,
                        int d, int H, int variant, int accumulate, float* logp, double* sums,
                        void* workspace, hipStream_t s) {
@@ -354,27 +379,17 @@ static int made_launch(const float* packed, const float* in, float* out, float* 
                                         sums, gauss_const(d));
         return check_launch("made_wide_kernel");  // (LOGP: the last workgroup wrote sums)
     }
-    if ((variant == NFX_MAF_INVERSE || variant == NFX_IAF_FORWARD) && d <= kTileMaxD) {
+    if (tile_path(d, HT, variant)) {
         const int64_t ntiles = (B + 31) / 32;
-        // 8 waves per workgroup (two per SIMD) while the batch fills the chip. Below that (no
-        // fused log_prob) as few waves per workgroup as spread the tiles one wave per SIMD, the
-        // weights read through L2 rather than staged per workgroup: 6x IAF(2, 64) sampling at
-        // n = 4,000 112 -> 73 us; staging the weights per workgroup measured no better at d = 63
-        // (profiles/r06_tile/)
-        int nw = 8;
-        if (!fused && ntiles < 4 * (int64_t)num_cus()) nw = (int)((ntiles + num_cus() - 1) / num_cus());
-        const size_t wbytes = (size_t)L.par_total * sizeof(float);
-        const size_t tiles = nw * 32 * (size_t)kTileStride * sizeof(float);
-        const bool wlds = nw == 8 && wbytes + tiles <= kLdsBytes;
-        made_par_kernel_t k = pick_tile(HT, wlds, variant, fused);
+        const TileConfig c = tile_config(L, ntiles, fused);
+        made_par_kernel_t k = pick_tile(HT, c.wlds, variant, fused);
         if (!k) return set_error(NFX_EUNSUPPORTED, "made_affine: no kernel for H=%d", H);
-        const size_t lds = (wlds ? wbytes : 0) + tiles;
-        int rc = prepare_lds((const void*)k, lds);
+        int rc = prepare_lds((const void*)k, c.lds);
         if (rc) return rc;
-        int grid = resident_grid((const void*)k, 64 * nw, lds, (ntiles + nw - 1) / nw);
+        int grid = resident_grid((const void*)k, 64 * c.nw, c.lds, (ntiles + c.nw - 1) / c.nw);
         if (grid > kMaxPartials) grid = kMaxPartials;
-        k<<<grid, 64 * nw, lds, s>>>(packed, in, out, log_det, B, d, accumulate, ntiles, logp, partials, sums,
-                                     gauss_const(d));
+        k<<<grid, 64 * c.nw, c.lds, s>>>(packed, in, out, log_det, B, d, accumulate, ntiles, logp, partials, sums,
+                                         gauss_const(d));
         return check_launch("made_tile_kernel");
     }
     if (variant == NFX_MAF_INVERSE || variant == NFX_IAF_FORWARD) {
@@ -451,4 +466,32 @@ extern "C" int nfx_made_affine_logprob(const float* packed, const float* in, flo
     if (!sums) return set_error(NFX_EINVAL, "made_affine_logprob: null sums");
     return made_launch(packed, in, out, log_det, B, d, H, variant, accumulate, logp, sums, workspace,
                        (hipStream_t)stream);
+}
+
+extern "C" int nfx_made_sample_supported(int d, int H, int variant) {
+    return (H > 0 && tile_path(d, (H + 31) / 32, variant) && variant == NFX_IAF_FORWARD) ? 1 : 0;
+}
+
+extern "C" int nfx_made_affine_sample(const float* packed, uint64_t seed, uint64_t* rng_state, float* z, float* x,
+                                      float* log_det, int64_t B, int d, int H, void* stream) {
+    if (B < 0 || d <= 0 || H <= 0) return set_error(NFX_EINVAL, "made_affine_sample: bad shape");
+    if (!nfx_made_sample_supported(d, H, NFX_IAF_FORWARD))
+        return set_error(NFX_EUNSUPPORTED, "made_affine_sample: d=%d H=%d outside the tile kernel (d <= %d, H <= 128)",
+                         d, H, kTileMaxD);
+    if (B == 0) return NFX_OK;
+    if (!packed || !rng_state || !z || !x || !log_det) return set_error(NFX_EINVAL, "made_affine_sample: null pointer");
+    if (z == x) return set_error(NFX_EINVAL, "made_affine_sample: z and x must not alias");
+    const int HT = (H + 31) / 32;
+    const MadeLayout L = made_layout(d, HT);
+    const int64_t ntiles = (B + 31) / 32;
+    const TileConfig c = tile_config(L, ntiles, false);
+    made_sample_kernel_t k = HT == 1 ? made_tile_sample_pick_ht<1>(c.wlds) : HT == 2 ? made_tile_sample_pick_ht<2>(c.wlds)
+                             : HT == 3 ? made_tile_sample_pick_ht<3>(c.wlds) : made_tile_sample_pick_ht<4>(c.wlds);
+    int rc = prepare_lds((const void*)k, c.lds);
+    if (rc) return rc;
+    int grid = resident_grid((const void*)k, 64 * c.nw, c.lds, (ntiles + c.nw - 1) / c.nw);
+    if (grid > kMaxPartials) grid = kMaxPartials;  // < kRngMaxGrid: rng_commit's count field
+    k<<<grid, 64 * c.nw, c.lds, (hipStream_t)stream>>>(packed, nullptr, x, log_det, B, d, 0, ntiles, nullptr, nullptr,
+                                                       nullptr, 0.f, MadeDraw{seed, rng_state, z});
+    return check_launch("made_tile_kernel");
 }

@@ -16,6 +16,7 @@
 // global/L2 otherwise (e.g. d=784 IAF).
 #pragma once
 #include "nfx_common.h"
+#include "nfx_rng.h"
 
 namespace nfx {
 
@@ -606,11 +607,43 @@ __device__ __forceinline__ void out_pair_n(int n, const float* __restrict__ W, c
     }
 }
 
-template <int HT, bool WLDS, int VAR, bool LOGP>
+// SAMPLE (IAF forward, first layer of a sampling stack, no accumulate): the rows are not read
+// from `in` but drawn on the device — pf[r] of lane l is base_value(row 32 t + r, dim l) at the
+// generator offset rng[0] (nfx_rng.h; 0 for lanes >= d and rows >= B, what the range-checked
+// load returns there) — and also stored to `z`; the kernel ends with rng_commit. The draw
+// arguments ride in one trailing MadeDraw parameter that only SAMPLE instantiations have, so
+// every other instantiation keeps its signature and its code.
+struct MadeDraw {
+    uint64_t seed;
+    uint64_t* rng;  // device uint64[2] generator state (nfx_rng.h)
+    float* z;       // [B, d] the draws
+};
+__device__ __forceinline__ const MadeDraw& made_draw_arg(const MadeDraw& a) { return a; }
+// The 32 rows of tile tt (wave-uniform) as the tile kernel holds them: pf[r] of lane l = the base
+// value of (row 32 tt + r, dim l); 0 past the batch, past d and past the last tile.
+__device__ __forceinline__ void made_draw_tile(float (&pf)[32], int64_t tt, int64_t ntiles, int64_t B, int d,
+                                               uint64_t seed, uint64_t off) {
+    const int lane = lane_id();
+    const bool live = tt < ntiles;
+#pragma unroll
+    for (int r = 0; r < 32; ++r) {
+        const int64_t row = tt * 32 + r;
+        pf[r] = 0.f;
+        if (live && row < B) {  // wave-uniform
+            const float v = base_value(row, lane, seed, off);
+            pf[r] = lane < d ? v : 0.f;
+        }
+    }
+}
+
+template <int HT, bool WLDS, int VAR, bool LOGP, bool SAMPLE = false, typename... DRAW>
 __global__ __launch_bounds__(512) void made_tile_kernel(
     const float* __restrict__ packed, const float* __restrict__ in, float* __restrict__ out,
     float* __restrict__ logdet, int64_t B, int d, int accumulate, int64_t ntiles,
-    float* __restrict__ logp, double* __restrict__ partials, double* __restrict__ sums, float cgauss) {
+    float* __restrict__ logp, double* __restrict__ partials, double* __restrict__ sums, float cgauss,
+    DRAW... draw) {
+    static_assert(sizeof...(DRAW) == (SAMPLE ? 1 : 0), "SAMPLE kernels take one MadeDraw");
+    static_assert(!SAMPLE || (VAR == NFX_IAF_FORWARD && !LOGP), "SAMPLE: the IAF forward pass");
     const MadeLayout L = made_layout(d, HT);
     constexpr int S = kTileStride;
     extern __shared__ f32x4 lds4[];
@@ -649,7 +682,11 @@ __global__ __launch_bounds__(512) void made_tile_kernel(
     double lpacc = 0.0;
     float pf[32];
     float ldpf = 0.f;  // incoming log-det of the lane's sample (accumulate), prefetched too
-    {
+    uint64_t draw_off = 0;
+    if constexpr (SAMPLE) {
+        draw_off = rng_offset(made_draw_arg(draw...).rng);
+        made_draw_tile(pf, t, ntiles, B, d, made_draw_arg(draw...).seed, draw_off);
+    } else {
         if (accumulate && t < ntiles && lane < 32 && t * 32 + col < B) ldpf = logdet[t * 32 + col];
         const int64_t rows = t < ntiles ? (B - t * 32 < 32 ? B - t * 32 : 32) : 0;
         const auto rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in) + (t < ntiles ? t * 32 * d : 0), 0,
@@ -669,6 +706,13 @@ __global__ __launch_bounds__(512) void made_tile_kernel(
         for (int r = 0; r < 32; ++r) {
             xt[r * S + lane] = pf[r];
             xmax = tmax(xmax, fabsf(pf[r]));  // NaN-propagating: a NaN fails the test
+        }
+        if constexpr (SAMPLE) {  // the draws to z, by the output rows' range-checked stores
+            const auto rs = __builtin_amdgcn_make_buffer_rsrc(made_draw_arg(draw...).z + base * d, 0, rows * rowb,
+                                                              0x00020000);
+#pragma unroll
+            for (int r = 0; r < 32; ++r)
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pf[r]), rs, voff, r * rowb, 0);
         }
         const bool dense = __builtin_amdgcn_ballot_w64(!(xmax <= tsafe)) != 0;
         wave_lds_sync();
@@ -697,7 +741,9 @@ __global__ __launch_bounds__(512) void made_tile_kernel(
 
         // prefetch the next tile's rows (and incoming log-det) while layer 4 runs
         const float ldin = ldpf;
-        {
+        if constexpr (SAMPLE) {
+            made_draw_tile(pf, t + nwaves, ntiles, B, d, made_draw_arg(draw...).seed, draw_off);
+        } else {
             const int64_t tn = t + nwaves;
             ldpf = (accumulate && tn < ntiles && lane < 32 && tn * 32 + col < B) ? logdet[tn * 32 + col] : 0.f;
             const int64_t rn = tn < ntiles ? (B - tn * 32 < 32 ? B - tn * 32 : 32) : 0;
@@ -762,6 +808,9 @@ __global__ __launch_bounds__(512) void made_tile_kernel(
     if constexpr (LOGP) {
         logp_commit<512>(lpacc, partials, sums, B);
     }
+    if constexpr (SAMPLE) {
+        rng_commit(made_draw_arg(draw...).rng);  // every workgroup read the offset in its prologue
+    }
 }
 
 typedef void (*made_par_kernel_t)(const float*, const float*, float*, float*, int64_t, int, int, int64_t,
@@ -773,5 +822,10 @@ template <int HT>
 made_par_kernel_t made_tile_pick_ht(bool wlds, int variant, bool logp);
 template <int HT>
 made_seq_kernel_t made_seq_pick_ht(int variant);
+// made_tile_kernel<HT, WLDS, NFX_IAF_FORWARD, false, true> (nfx_made_sample.hip)
+typedef void (*made_sample_kernel_t)(const float*, const float*, float*, float*, int64_t, int, int, int64_t, float*,
+                                     double*, double*, float, MadeDraw);
+template <int HT>
+made_sample_kernel_t made_tile_sample_pick_ht(bool wlds);
 
 }  // namespace nfx

@@ -64,8 +64,8 @@ __global__ __launch_bounds__(64 * NW) void spline_schain_kernel(
         const int64_t s1 = s0 + slice_chunks < c1 ? s0 + slice_chunks : c1;
         const int64_t r0 = s0 * 64;
         const int rows = (int)((B < s1 * 64 ? B : s1 * 64) - r0);
-        if (rng) {  // the fused sampling pass: z ~ N(0, I) drawn here (base_draw, nfx_chain.h)
-            const uint64_t off = __hip_atomic_load(rng, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (rng) {  // the fused sampling pass: z ~ N(0, I) drawn here (base_draw, nfx_rng.h)
+            const uint64_t off = rng_offset(rng);
             for (int e = threadIdx.x; e < rows; e += NTH) {
                 float z[D];
                 base_draw<D>(r0 + e, seed, off, z);
@@ -186,20 +186,7 @@ __global__ __launch_bounds__(64 * NW) void spline_schain_kernel(
     if constexpr (LOGP) {
         logp_commit<NTH>(lpacc, partials, sums, B);
     }
-    if (rng) {  // every workgroup read rng[0] in its slices; the last one to get here moves it on
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            uint64_t* cnt = rng + 1;
-            const uint64_t prev = __hip_atomic_fetch_add(cnt, (uint64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (prev == (uint64_t)gridDim.x - 1) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                __hip_atomic_store(rng, __hip_atomic_load(rng, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1,
-                                   __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(cnt, (uint64_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+    if (rng) rng_commit(rng);  // every workgroup read rng[0] in its slices; the last one here moves it on
 }
 
 typedef void (*spline_schain_t)(NfxChainPacks, int, const float*, float*, float*, int64_t, SplineConsts, int, int64_t,

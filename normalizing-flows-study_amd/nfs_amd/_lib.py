@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "nfx_rqs_unit", "nfx_rqs_unit_backward",
     "nfx_arqs_packed_floats", "nfx_arqs_pack", "nfx_arqs",
     "nfx_made_packed_floats", "nfx_made_pack", "nfx_made_pack_parallel", "nfx_made_pack_sequential", "nfx_made_affine", "nfx_made_affine_logprob", "nfx_made_seq_policy",
+    "nfx_base_normal", "nfx_made_sample_supported", "nfx_made_affine_sample",
     "nfx_made_pack_backward", "nfx_made_backward_factor_floats", "nfx_made_backward_max_batch",
     "nfx_made_affine_backward",
     "nfx_made_seq_backward", "nfx_made_factor_pitch", "nfx_made_param_floats", "nfx_made_wgrad_workspace_bytes", "nfx_made_backward_weights",
@@ -165,6 +166,9 @@ _SIGNATURES = {
     "nfx_made_pack_parallel": (_int, [ctypes.POINTER(NfxMlpRaw), _int, _int, _vp, _vp]),
     "nfx_made_pack_sequential": (_int, [_int, _int, _vp, _vp]),
     "nfx_made_seq_policy": (_int, [_int]),
+    "nfx_base_normal": (_int, [ctypes.c_uint64, _vp, _vp, _i64, _int, _vp]),
+    "nfx_made_sample_supported": (_int, [_int, _int, _int]),
+    "nfx_made_affine_sample": (_int, [_vp, ctypes.c_uint64, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp]),
     "nfx_made_affine": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "nfx_made_affine_logprob": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "nfx_made_pack_backward": (_int, [ctypes.POINTER(NfxMlpRaw), _int, _int, _vp, _vp]),

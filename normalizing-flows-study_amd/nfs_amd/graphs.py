@@ -13,9 +13,12 @@ and the reference's sampling throughput loop, plots/_common.py:217-222,264-274):
 drawn on the device and forward(z) runs in one graph launch per batch of samples, no host round
 trip. For chains of eval CouplingLayers (RealNVP) the draw is fused INTO the chain kernel
 (nfx_affine_chain_sample: Philox4x32-10 in the kernel's prologue, the generator state advanced on
-the device, so every replay draws afresh — the graph holds one kernel); other models draw with
-torch's graph-safe Philox generator (normal_) ahead of their forward. The example tensor only
-gives the shape [n, d]; `static_in` holds the last z.
+the device, so every replay draws afresh — the graph holds one kernel), as it is for d = 2 spline
+chains and for stacks that start with an IAF layer of a tile-kernel shape (`fused_draw`); every
+other model with `sample_on_device` draws with the library's stand-alone kernel (nfx_base_normal,
+the same generator) ahead of its forward chain, one more launch. Only models without that method
+draw with torch's graph-safe Philox generator (normal_). The example tensor only gives the shape
+[n, d]; `static_in` holds the last z.
 
 The packed weight images are built before capture and baked into the graph. With
 `strict=True` (default) every call checks that no parameter or buffer changed since capture
@@ -78,12 +81,16 @@ class GraphedFlow:
     def _call(self):
         if self.mode == "sample":
             n = self.static_in.shape[0]
-            if hasattr(self.model, "sample_fused_ok") and self.model.sample_fused_ok(n, self.static_in.device):
-                if not hasattr(self, "_sx"):
+            dev = self.static_in.device
+            if hasattr(self.model, "sample_on_device"):
+                # fused_draw: the draw happens inside the first forward kernel; otherwise the
+                # stand-alone draw kernel runs ahead of the forward chain (one more launch)
+                self.fused_draw = bool(self.model.sample_fused_ok(n, dev))
+                if self.fused_draw and not hasattr(self, "_sx"):
                     self._sx = torch.empty_like(self.static_in)
-                    self._sld = torch.empty(n, device=self.static_in.device)
-                self.fused_draw = True
-                x, ld, _ = self.model.sample_fused(n, self.static_in.device, out=(self.static_in, self._sx, self._sld))
+                    self._sld = torch.empty(n, device=dev)
+                out = (self.static_in, self._sx, self._sld) if self.fused_draw else (self.static_in, None, None)
+                x, ld, _ = self.model.sample_on_device(n, dev, out=out)
                 return x, ld
             self.fused_draw = False
             self.static_in.normal_()

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import _lib
 from ..distributed import merge_bn_stats, sync_bn_world
+from ..flows import autoregressive as _autoregressive
 from ..flows import coupling as _coupling
 from ..flows import spline as _spline
 from ..flows.flow import HipFlow, STATS
@@ -220,11 +221,21 @@ class NormalizingFlowModel(nn.Module):
         return (logp, sums) if return_sums else logp
 
     # -- sampling with the base draw on the device ---------------------------------------------
+    # z ~ N(0, I) comes from the library's own counter-based generator (csrc/nfx_rng.h): the model
+    # keeps, per device, `_nfx_rng[device] = (seed, state)` with state a device uint64[2] = [offset,
+    # arrival word]. Every draw reads the offset and advances it by one ON THE DEVICE, so eager
+    # calls and replays of a captured graph both draw afresh. Calls sharing one model's state must
+    # be stream-ordered (two streams drawing at once would read the same offset).
     def sample_fused_ok(self, num_samples, device):
-        """True when sample_fused runs as one kernel: eval-mode CouplingLayers (d in {2, 4, 8},
-        H <= 128, up to 64k samples) or d = 2 SplineCouplingLayers (any batch), no between-layer
+        """True when sample_fused draws INSIDE the first forward kernel: eval-mode CouplingLayers
+        (d in {2, 4, 8}, H <= 128, up to 64k samples) or d = 2 SplineCouplingLayers (any batch) as
+        one launch for the whole stack, or a stack whose first layer is an
+        InverseAutoregressiveFlow of a shape the IAF tile kernel takes (the library says which:
+        nfx_made_sample_supported) with the remaining layers launched one by one. No between-layer
         BatchNorm."""
-        return not self.batch_norm_between_layers and self._sample_chain(num_samples, device) is not None
+        if self.batch_norm_between_layers:
+            return False
+        return self._sample_chain(num_samples, device) is not None or self._sample_iaf_ok(num_samples, device)
 
     def _sample_chain(self, num_samples, device):
         fl = list(self.flows)
@@ -233,25 +244,69 @@ class NormalizingFlowModel(nn.Module):
                 return m
         return None
 
-    def sample_fused(self, num_samples, device="cuda", out=None):
-        """Flow.sample (src/flows/flow/flow.py:40-54) with the N(0, I) base draw fused into the
-        sampling forward: z ~ N(0, I) on the device (Philox4x32-10, this model's own generator
-        state, seeded from torch's CPU generator on first use) and x = forward(z), ONE launch
-        (nfx_affine_chain_sample / nfx_spline_chain_sample). Returns (x, log_det, z); x equals
-        forward(z) bit for bit.
-        out=(z, x, ld) writes into caller buffers (GraphedFlow(mode="sample"))."""
+    def _sample_iaf_ok(self, num_samples, device):
         dev = torch.device(device)
-        if dev.type == "cuda" and dev.index is None:
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if not self.sample_fused_ok(num_samples, dev):
-            raise NotImplementedError("sample_fused: the fused sampling chain does not take this model / size")
+        if self.training or num_samples <= 0 or dev.type != "cuda" or len(self.flows) == 0:
+            return False
+        f0 = self.flows[0]
+        if not isinstance(f0, _autoregressive.InverseAutoregressiveFlow) or not f0._fused_family():
+            return False
+        if not _lib.lib().nfx_made_sample_supported(f0.dim, f0.conditioner.hidden_dim, _lib.NFX_IAF_FORWARD):
+            return False
+        return self._sample_forward_ok(dev)
+
+    def _sample_forward_ok(self, dev):
+        """Would the no-grad forward of an fp32 [n, d] tensor on `dev` run the HIP chain?"""
+        d = getattr(self.flows[0], "data_dim", None) if len(self.flows) else None
+        if dev.type != "cuda" or d is None:
+            return False
+        with torch.no_grad():
+            return self._hip_chain_ok(torch.empty(0, d, device=dev))
+
+    def _sampler_state(self, dev):
         st = getattr(self, "_nfx_rng", None)
         if st is None:
             st = self._nfx_rng = {}
         if dev not in st:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            seed = getattr(self, "_nfx_seed", None)  # seed_sampler(seed) before the first draw
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             st[dev] = (seed, torch.zeros(2, dtype=torch.int64, device=dev))
-        seed, state = st[dev]
+        return st[dev]
+
+    def seed_sampler(self, seed, device=None):
+        """Set the seed of this model's sampling generator and put its offset back to 0: the draws
+        that follow are a function of (seed, number of draws since) alone. device=None: every
+        device the model has drawn on, and every device it draws on later."""
+        seed = int(seed) & ((1 << 64) - 1)
+        st = getattr(self, "_nfx_rng", None)
+        if st is None:
+            st = self._nfx_rng = {}
+        if device is None:
+            self._nfx_seed = seed
+        devs = list(st) if device is None else [_cuda_device(device)]
+        for dev in devs:
+            if dev in st:
+                st[dev][1].zero_()
+                st[dev] = (seed, st[dev][1])
+            else:
+                st[dev] = (seed, torch.zeros(2, dtype=torch.int64, device=dev))
+
+    def sample_fused(self, num_samples, device="cuda", out=None):
+        """Flow.sample (src/flows/flow/flow.py:40-54) with the N(0, I) base draw fused into the
+        sampling forward: z ~ N(0, I) on the device (Philox4x32-10, this model's own generator
+        state, seeded from torch's CPU generator on first use or by seed_sampler) and
+        x = forward(z). Coupling and spline stacks: ONE launch (nfx_affine_chain_sample /
+        nfx_spline_chain_sample). Stacks that start with an IAF layer: the draw in that layer's
+        kernel (nfx_made_affine_sample), the remaining layers launched one by one — L launches
+        for L layers. Returns (x, log_det, z); x and log_det equal forward(z) bit for bit.
+        out=(z, x, ld) writes into caller buffers (GraphedFlow(mode="sample")). Calls sharing
+        this model's generator state must be stream-ordered."""
+        dev = _cuda_device(device)
+        if not self.sample_fused_ok(num_samples, dev):
+            raise NotImplementedError("sample_fused: no kernel with the draw fused in takes this model / size "
+                                      "(sample_on_device draws with the stand-alone kernel)")
+        seed, state = self._sampler_state(dev)
         d = self.flows[0].data_dim
         if out is None:
             z = torch.empty(num_samples, d, device=dev)
@@ -259,7 +314,63 @@ class NormalizingFlowModel(nn.Module):
             ld = torch.empty(num_samples, device=dev)
         else:
             z, x, ld = out
-        self._sample_chain(num_samples, dev).chain_sample(list(self.flows), state, seed, z, x, ld)
+        chain = self._sample_chain(num_samples, dev)
+        if chain is not None:
+            chain.chain_sample(list(self.flows), state, seed, z, x, ld)
+            return x, ld, z
+        # IAF first: layer i writes x when an even number of layers follow it, else the spare
+        # buffer, so the last layer lands in x and no launch reads the buffer it writes
+        n = len(self.flows)
+        spare = torch.empty_like(x) if n > 1 else None
+        f0 = self.flows[0]
+        cur = x if (n - 1) % 2 == 0 else spare
+        packed = f0._packed(dev, f0._build_pack)
+        _lib.check(_lib.lib().nfx_made_affine_sample(
+            _lib.ptr(packed), seed & ((1 << 64) - 1), _lib.ptr(state), _lib.ptr(z), _lib.ptr(cur), _lib.ptr(ld),
+            num_samples, d, f0.conditioner.hidden_dim, _lib.stream_of(x)), "nfx_made_affine_sample")
+        STATS["hip"] += 1
+        with torch.no_grad():
+            for i in range(1, n):
+                nxt = x if (n - 1 - i) % 2 == 0 else spare
+                self.flows[i]._hip_launch_counted(cur, nxt, ld, 1, accumulate=True)
+                cur = nxt
+        return x, ld, z
+
+    def sample_on_device(self, num_samples, device="cuda", out=None):
+        """z ~ N(0, I) drawn on the device and x, log_det = forward(z), for EVERY model whose
+        no-grad fp32 forward runs the HIP chain: sample_fused where a kernel fuses the draw
+        (sample_fused_ok); otherwise the stand-alone draw kernel (nfx_base_normal — the same
+        values the fused kernels draw at that seed and offset) into z, then the forward chain on
+        z. Between-layer BatchNorm in eval mode is a fixed map and is fine. Raises
+        NotImplementedError only where forward itself would leave the HIP kernels (train-mode
+        BatchNorm, a CPU device). Returns (x, log_det, z).
+        out=(z, x, ld): caller buffers; x and ld may be None (outside the fused path they are
+        then the forward chain's own outputs, which saves two copies). Calls sharing this model's
+        generator state must be stream-ordered."""
+        dev = _cuda_device(device)
+        if self.sample_fused_ok(num_samples, dev):
+            if out is not None and (out[1] is None or out[2] is None):
+                z = out[0]
+                out = (z, torch.empty_like(z) if out[1] is None else out[1],
+                       torch.empty(num_samples, device=dev) if out[2] is None else out[2])
+            return self.sample_fused(num_samples, dev, out)
+        if not self._sample_forward_ok(dev):
+            raise NotImplementedError("sample_on_device: forward of this model does not run the HIP chain on "
+                                      f"{dev} (train-mode BatchNorm, or not a ROCm device)")
+        seed, state = self._sampler_state(dev)
+        d = self.flows[0].data_dim
+        z = torch.empty(num_samples, d, device=dev) if out is None else out[0]
+        if z.shape != (num_samples, d) or z.dtype != torch.float32 or z.device != dev or not z.is_contiguous():
+            raise ValueError(f"sample_on_device: z must be a contiguous fp32 [{num_samples}, {d}] tensor on {dev}")
+        _lib.check(_lib.lib().nfx_base_normal(seed & ((1 << 64) - 1), _lib.ptr(state), _lib.ptr(z), num_samples, d,
+                                              _lib.stream_of(z)), "nfx_base_normal")
+        STATS["hip"] += 1
+        with torch.no_grad():
+            x, ld = self._hip_chain(z, 1)
+            if out is not None and out[1] is not None:
+                x = out[1].copy_(x)
+            if out is not None and out[2] is not None:
+                ld = out[2].copy_(ld)
         return x, ld, z
 
     def nll(self, x):
@@ -267,6 +378,14 @@ class NormalizingFlowModel(nn.Module):
         _, sums = self.log_prob(x, return_sums=True)
         s = sums.cpu()
         return -(s[0] / s[1]).item()
+
+
+def _cuda_device(device):
+    """torch.device(device) with the current index filled in for a bare "cuda"."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
 
 
 _GAUSS_WS = collections.OrderedDict()

@@ -38,3 +38,9 @@ class RealNVP(nn.Module):
 
     def sample_fused(self, num_samples, device="cuda", out=None):
         return self.flow.sample_fused(num_samples, device, out)
+
+    def sample_on_device(self, num_samples, device="cuda", out=None):
+        return self.flow.sample_on_device(num_samples, device, out)
+
+    def seed_sampler(self, seed, device=None):
+        return self.flow.seed_sampler(seed, device)

@@ -1,6 +1,8 @@
 """Per-layer kernels of the reference's MADE sampling figure models (6x IAF(2,64) forward =
 parallel, 6x MAF(2,64) forward = sequential) at n = 4,000: kernel name and event-timed launch per
-layer, per sequential policy for MAF.
+layer, per sequential policy for MAF; then, per model, replays of the captured sampling graph
+GraphedFlow(mode="sample") (the base draw + the 6 layers; `fused_draw`: the draw runs inside the
+first layer's kernel), median of 5 batches of 100 replays.
     python tools/made_sample_timing.py"""
 import json
 import os
@@ -43,4 +45,19 @@ for kind in ("iaf", "maf"):
         per = sum(a.elapsed_time(b) for _, a, b in rec) / len(rec) * 1e3
         print(json.dumps({"model": f"6x{kind.upper()}(2,64)", "policy": name, "kernels": ks, "layer_us": round(per, 1),
                           "forward_us": round(e0.elapsed_time(e1) / 50 * 1e3, 1)}), flush=True)
-_lib.lib().nfx_made_seq_policy(_lib.NFX_MADE_SEQ_AUTO)
+    _lib.lib().nfx_made_seq_policy(_lib.NFX_MADE_SEQ_AUTO)
+    g = nfs_amd.GraphedFlow(m, torch.empty(n, 2, device="cuda"), mode="sample")
+    for _ in range(20):
+        g()
+    us = []
+    for _ in range(5):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(100):
+            g()
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(e0.elapsed_time(e1) / 100 * 1e3)
+    print(json.dumps({"model": f"6x{kind.upper()}(2,64)", "graph": "sample", "fused_draw": bool(g.fused_draw),
+                      "launches": g.launches, "replay_us": round(sorted(us)[2], 1),
+                      "replay_us_min_max": [round(min(us), 1), round(max(us), 1)]}), flush=True)
