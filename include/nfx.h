@@ -632,6 +632,28 @@ int nfx_spline_elem_backward_bounded(const float* x, const float* params, const 
                                      float min_derivative, int direction, void* stream);
 int nfx_spline_rescale(const float* x, const float* bounds, float* xr, int64_t B, int d, float bound, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ContinuousFlow (src/flows/continuous/continuous_flow.py:6-138, ode_func.py:4-91): the ODE
+ *   dz/dt = v(z, t) = W3 tanh(W2 tanh(W1 [z; t] + b1) + b2) + b3,   dl/dt = +tr(dv/dz)
+ * integrated from t_begin to t_end by the fixed-grid 3/8-rule RK4 of the reference's solver
+ * (odeint method 'rk4', options step_size) in one launch. w1 [H, d+1] (time is the LAST input
+ * column), b1 [H], w2 [H, H], b2 [H], w3 [d, H], b3 [d]: the nn.Linear tensors, row-major.
+ * Grid, in fp32: n = ceil((t_end - t_begin) / step_size + 1) points k * step_size + t_begin, the
+ * last one pinned to t_end (a short last step); t_begin > t_end integrates the negated-time
+ * problem, i.e. the same grid walked downward; t_begin == t_end copies in to out with log-det 0.
+ * The divergence is the exact closed-form trace for every d (the reference estimates it with
+ * fresh noise for d > 2). After the last step: a non-finite output element returns its input
+ * element, a non-finite log-det becomes 0, both are clamped to [-10, 10]. Kernel family:
+ * 1 <= d <= 8, H in {32, 64, 128}, any B >= 1 (nfx_cnf_supported: 1 inside it, host-only check);
+ * NFX_EUNSUPPORTED elsewhere. accumulate adds the log-det into log_det.
+ * ------------------------------------------------------------------------------------- */
+size_t nfx_cnf_packed_floats(int d, int H);
+int nfx_cnf_pack(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                 const float* b3, int d, int H, float* packed, void* stream);
+int nfx_cnf_supported(int64_t B, int d, int H);
+int nfx_cnf_integrate(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,
+                      int H, float t_begin, float t_end, float step_size, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

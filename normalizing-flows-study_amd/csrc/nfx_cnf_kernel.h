@@ -1,0 +1,276 @@
+// Continuous normalizing flow: the whole fixed-step RK4 (3/8 rule) integration of
+//   dz/dt = v(z, t),  dl/dt = +tr(dv/dz),   v = W3 tanh(W2 tanh(W1 [z; t] + b1) + b2) + b3
+// in ONE launch (see nfx_cnf.hip for the design notes and the cost model).
+#pragma once
+#include "nfx_common.h"
+
+namespace nfx {
+
+// Packed weight image (floats), H = 32 HT, accumulator order = [tile][lane half][register]:
+//   w1  [HT][KS1][64]      A operand of layer 1 over k = 0..d ([z; t], t is input column d),
+//                          KS1 = (d + 2) / 2 k-steps, zero beyond k = d
+//   b1  [HT][2][16]        layer-1 bias in accumulator order
+//   b2  [HT][2][16]
+//   w3  [d][HT][2][16]     W3[j, :] in accumulator order (VALU dots)
+//   b3  [up4(d)]
+//   c2  [HT][HT][4][64][4] A operand of the trace product, in w2's order: C = W2 * (W3^T W1[:, :d]^T)
+//                          elementwise, so that tr(dv/dz) = g2^T C g1 (nfx_cnf.hip)
+//   w2  [HT][HT][4][64][4] A operand of layer 2: [out tile][k tile][r/4][lane][r%4]
+// Everything before w2 is staged in LDS; w2 lives in registers for H <= 64 and in LDS for H = 128.
+struct CnfLayout {
+    int d, HT, KS1;
+    int w1, b1, b2, w3, b3, c2, w2, total;
+};
+
+__host__ __device__ constexpr CnfLayout cnf_layout(int d, int HT) {
+    CnfLayout L{};
+    L.d = d;
+    L.HT = HT;
+    L.KS1 = (d + 2) / 2;
+    int o = 0;
+    L.w1 = o; o += HT * L.KS1 * 64;
+    L.b1 = o; o += HT * 32;
+    L.b2 = o; o += HT * 32;
+    L.w3 = o; o += d * HT * 32;
+    L.b3 = o; o += (d + 3) & ~3;
+    L.c2 = o; o += HT * HT * 1024;
+    L.w2 = o; o += HT * HT * 1024;
+    L.total = o;
+    return L;
+}
+
+struct CnfArgs {
+    const float* packed;
+    const float* in;
+    float* out;
+    float* logdet;
+    int64_t B, ntiles;
+    int accumulate;
+    int nsteps;         // grid points - 1; 0: equal times, the identity
+    float s0, s1, h;    // ascending grid s_k = k h + s0, last point s1
+    float sgn;          // t = sgn * s: -1 walks the grid downward (t_begin > t_end)
+};
+
+constexpr int kCnfMaxD = 8;
+
+// Waves per SIMD the launch really reaches: two for H <= 64 (<= 256 registers; a handful of
+// outer-loop spills at H = 64, d >= 6), one for H = 128 (the register file to itself, no scratch).
+constexpr int cnf_waves_per_simd(int HT) { return HT <= 2 ? 2 : 1; }
+
+template <int HT, int D>
+__global__ __launch_bounds__(256)
+__attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT)))) void cnf_kernel(CnfArgs A) {
+    constexpr CnfLayout L = cnf_layout(D, HT);
+    constexpr int KS1 = L.KS1;
+    constexpr bool W2REG = HT <= 2;
+    constexpr int NLDS = W2REG ? L.w2 : L.total;
+    extern __shared__ f32x4 lds4[];
+    {
+        const f32x4* src = reinterpret_cast<const f32x4*>(A.packed);
+        for (int i = threadIdx.x; i < NLDS / 4; i += blockDim.x) lds4[i] = src[i];
+    }
+    __syncthreads();
+    const float* sm = reinterpret_cast<const float*>(lds4);
+
+    const int lane = lane_id(), h = lane >> 5, col = lane & 31;
+    const int nw = blockDim.x >> 6;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+    // W2 as the layer-2 A operand: 16 HT^2 floats per lane, loaded once (H <= 64)
+    f32x4 w2r[W2REG ? HT * HT * 4 : 1];
+    if constexpr (W2REG) {
+        const f32x4* wg = reinterpret_cast<const f32x4*>(A.packed + L.w2) + lane;
+#pragma unroll
+        for (int g = 0; g < HT * HT * 4; ++g) w2r[g] = wg[g * 64];
+    }
+    const f32x4* w2s = reinterpret_cast<const f32x4*>(sm + L.w2) + lane;
+    const f32x4* c2s = reinterpret_cast<const f32x4*>(sm + L.c2) + lane;
+
+    // One evaluation of the field and its exact divergence for the wave's 32 samples. Both lane
+    // halves hold the same state (sample col); they own different hidden-unit rows of every
+    // accumulator tile and meet in halves_sum. The divergence sum_i W3[i, :] . (g2 * (W2 (g1 *
+    // W1[:, i]))) is summed over i inside the weights: it equals g2 . (C g1), ONE more H x H product
+    // beside layer 2 instead of d.
+    auto field = [&](float t, const float (&z)[D], float (&v)[D], float& tr) {
+        const int oz = opaque_zero();  // no hoisting of the LDS operands out of the step loop
+        const float* s = sm + oz;
+        const f32x4* w2l = w2s + oz;
+        const f32x4* c2l = c2s + oz;
+        float xb[KS1];
+#pragma unroll
+        for (int ks = 0; ks < KS1; ++ks) {
+            const int k0 = 2 * ks, k1 = 2 * ks + 1;
+            const float a = k0 < D ? z[k0 < D ? k0 : 0] : (k0 == D ? t : 0.f);
+            const float b = k1 < D ? z[k1 < D ? k1 : 0] : (k1 == D ? t : 0.f);
+            xb[ks] = h ? b : a;
+        }
+        f32x16 h1[HT];
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) {
+            f32x16 a = load_bias16(s + L.b1 + ht * 32, h);
+#pragma unroll
+            for (int ks = 0; ks < KS1; ++ks) a = mfma32(s[L.w1 + (ht * KS1 + ks) * 64 + lane], xb[ks], a);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) h1[ht][r] = tanhf(a[r]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        float pv[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) pv[j] = 0.f;
+        float ptr = 0.f;
+#pragma unroll
+        for (int hto = 0; hto < HT; ++hto) {
+            auto w2 = [&](int kt, int rq) -> f32x4 {
+                if constexpr (W2REG) return w2r[(hto * HT + kt) * 4 + rq];
+                else return w2l[((hto * HT + kt) * 4 + rq) * 64];
+            };
+            // h2 tile hto, and beside it the same tile of C g1 (g1 = 1 - h1^2): two independent chains
+            f32x16 a = load_bias16(s + L.b2 + hto * 32, h);
+            f32x16 c = {};
+#pragma unroll
+            for (int kt = 0; kt < HT; ++kt)
+#pragma unroll
+                for (int rq = 0; rq < 4; ++rq) {
+                    const f32x4 w = w2(kt, rq);
+                    const f32x4 cw = c2l[((hto * HT + kt) * 4 + rq) * 64];
+#pragma unroll
+                    for (int rr = 0; rr < 4; ++rr) {
+                        const float hv = h1[kt][4 * rq + rr];
+                        a = mfma32(w[rr], hv, a);
+                        c = mfma32(cw[rr], fmaf(-hv, hv, 1.f), c);
+                    }
+                }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float th = tanhf(a[r]);
+                a[r] = th;
+                ptr = fmaf(fmaf(-th, th, 1.f), c[r], ptr);
+            }
+            // (the barriers keep the compiler from issuing every LDS operand of the evaluation
+            // ahead of its use: that cost up to 256 AGPRs and scratch at H = 128)
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                __builtin_amdgcn_sched_barrier(0);
+                const f32x16 w3 = load_bias16(s + L.w3 + (j * HT + hto) * 32, h);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) pv[j] = fmaf(w3[r], a[r], pv[j]);
+                asm volatile("" : "+v"(pv[j]));  // the dots of row j end before the next barrier
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int j = 0; j < D; ++j) v[j] = halves_sum(pv[j], pv[j]) + s[L.b3 + j];
+        tr = halves_sum(ptr, ptr);
+    };
+
+    for (int64_t tile = (int64_t)blockIdx.x * nw + wave; tile < A.ntiles; tile += (int64_t)gridDim.x * nw) {
+        const int64_t srow = tile * 32 + col;
+        const bool live = srow < A.B;  // a dead column integrates zeros and is never stored
+        float x0[D], y[D];
+#pragma unroll
+        for (int j = 0; j < D; ++j) y[j] = x0[j] = live ? A.in[srow * D + j] : 0.f;
+        float ld = 0.f;
+        // State and log-det are carried across the steps as compensated (Kahan) sums: a hundred
+        // fp32 adds of increments ~1e-2 into values ~1 otherwise random-walk to a few ulp, which
+        // is the dominant error of an fp32 solve (the field's own rounding enters scaled by dt).
+        float yc[D], ldc = 0.f;
+#pragma unroll
+        for (int j = 0; j < D; ++j) yc[j] = 0.f;
+
+#pragma unroll 1
+        for (int k = 0; k < A.nsteps; ++k) {
+#pragma clang fp contract(off)  // every mul/add rounds separately, as the torch composite's ops
+            const float sk = (float)k * A.h + A.s0;
+            const float sk1 = k + 1 == A.nsteps ? A.s1 : (float)(k + 1) * A.h + A.s0;
+            const float t0 = A.sgn * sk, t1 = A.sgn * sk1;
+            const float dt = t1 - t0;
+            float k1[D], k2[D], k3[D], zin[D];
+            float l1 = 0.f, l2 = 0.f, l3 = 0.f;
+            float t = t0;
+#pragma unroll
+            for (int j = 0; j < D; ++j) zin[j] = y[j];
+#pragma unroll 1
+            for (int st = 0; st < 4; ++st) {
+                float v[D], tr;
+                field(t, zin, v, tr);
+                if (st == 0) {
+                    t = t0 + dt / 3.f;
+                    l1 = tr;
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        k1[j] = v[j];
+                        zin[j] = y[j] + dt * k1[j] / 3.f;
+                    }
+                } else if (st == 1) {
+                    t = t0 + 2.f * dt / 3.f;
+                    l2 = tr;
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        k2[j] = v[j];
+                        zin[j] = y[j] + dt * (k2[j] - k1[j] / 3.f);
+                    }
+                } else if (st == 2) {
+                    t = t1;
+                    l3 = tr;
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        k3[j] = v[j];
+                        zin[j] = y[j] + dt * (k1[j] - k2[j] + k3[j]);
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < D; ++j) {
+                        const float inc = (k1[j] + 3.f * (k2[j] + k3[j]) + v[j]) * dt * 0.125f - yc[j];
+                        const float sum = y[j] + inc;
+                        yc[j] = (sum - y[j]) - inc;
+                        y[j] = sum;
+                    }
+                    const float inc = (l1 + 3.f * (l2 + l3) + tr) * dt * 0.125f - ldc;
+                    const float sum = ld + inc;
+                    ldc = (sum - ld) - inc;
+                    ld = sum;
+                }
+            }
+        }
+
+        if (live && h == 0) {
+            float o[D];
+            float lo = ld;
+            if (A.nsteps > 0) {  // the guards (equal times return the input untouched)
+#pragma unroll
+                for (int j = 0; j < D; ++j) o[j] = tclamp(nonfinite(y[j]) ? x0[j] : y[j], -10.f, 10.f);
+                lo = tclamp(nonfinite(ld) ? 0.f : ld, -10.f, 10.f);
+            } else {
+#pragma unroll
+                for (int j = 0; j < D; ++j) o[j] = x0[j];
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) A.out[srow * D + j] = o[j];
+            A.logdet[srow] = A.accumulate ? A.logdet[srow] + lo : lo;
+        }
+    }
+}
+
+typedef void (*cnf_kernel_t)(CnfArgs);
+
+// One translation unit per hidden width (nfx_cnf_h{1,2,4}.hip).
+template <int HT>
+cnf_kernel_t cnf_pick_ht(int d);
+
+#define NFX_CNF_INSTANTIATE(HT)                                   \
+    template <>                                                   \
+    cnf_kernel_t cnf_pick_ht<HT>(int d) {                         \
+        switch (d) {                                              \
+            case 1: return cnf_kernel<HT, 1>;                     \
+            case 2: return cnf_kernel<HT, 2>;                     \
+            case 3: return cnf_kernel<HT, 3>;                     \
+            case 4: return cnf_kernel<HT, 4>;                     \
+            case 5: return cnf_kernel<HT, 5>;                     \
+            case 6: return cnf_kernel<HT, 6>;                     \
+            case 7: return cnf_kernel<HT, 7>;                     \
+            case 8: return cnf_kernel<HT, 8>;                     \
+            default: return nullptr;                              \
+        }                                                         \
+    }
+
+}  // namespace nfx

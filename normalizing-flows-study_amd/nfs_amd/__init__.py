@@ -6,11 +6,12 @@ src/models/*), backed by hand-written HIP kernels in libnfx.so (C-ABI: include/n
 from . import _lib
 from .flows import (Flow, SequentialFlow, CouplingLayer, SplineCouplingLayer,
                     rational_quadratic_spline, ARQS, MaskedLinear, MADE, MaskedAutoregressiveFlow,
-                    InverseAutoregressiveFlow, made_degrees, STATS, reset_stats)
+                    InverseAutoregressiveFlow, made_degrees, ODEFunc, ContinuousFlow, STATS,
+                    reset_stats)
 from .models import NormalizingFlowModel, RealNVP, RealNVPSpline, gauss_logprob
 from .graphs import GraphedFlow, GraphedTrainStep
 
 __all__ = ["Flow", "SequentialFlow", "CouplingLayer", "SplineCouplingLayer",
            "rational_quadratic_spline", "ARQS", "MaskedLinear", "MADE", "MaskedAutoregressiveFlow",
-           "InverseAutoregressiveFlow", "NormalizingFlowModel", "RealNVP", "RealNVPSpline",
+           "InverseAutoregressiveFlow", "ODEFunc", "ContinuousFlow", "NormalizingFlowModel", "RealNVP", "RealNVPSpline",
            "gauss_logprob", "made_degrees", "STATS", "reset_stats", "GraphedFlow", "GraphedTrainStep"]

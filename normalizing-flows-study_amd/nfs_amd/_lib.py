@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "nfx_made_elem_seq_backward", "nfx_made_elem_seq_step_backward", "nfx_made_elem_prefix",
     "nfx_affine_elem_forward", "nfx_affine_elem_backward", "nfx_bn_prepare", "nfx_bn_apply_relu",
     "nfx_bn_workspace_bytes", "nfx_bn_backward_sums", "nfx_bn_backward_apply", "nfx_arqs_step",
+    "nfx_cnf_packed_floats", "nfx_cnf_pack", "nfx_cnf_supported", "nfx_cnf_integrate",
 )
 
 
@@ -158,6 +159,10 @@ _SIGNATURES = {
                                         _int, _f, _f, _f, _f, _int, _vp]),
     "nfx_spline_chain_sample": (_int, [ctypes.POINTER(_vp), _int, ctypes.c_uint64, _vp, _vp, _vp, _vp, _i64, _int, _int,
                                        _int, _f, _f, _f, _f, _vp]),
+    "nfx_cnf_packed_floats": (_sz, [_int, _int]),
+    "nfx_cnf_pack": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "nfx_cnf_supported": (_int, [_i64, _int, _int]),
+    "nfx_cnf_integrate": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int,
                                      _vp]),

@@ -5,8 +5,9 @@ from .spline import SplineCouplingLayer, rational_quadratic_spline
 from .arqs import ARQS
 from .autoregressive import (MaskedLinear, MADE, MaskedAutoregressiveFlow,
                              InverseAutoregressiveFlow, made_degrees)
+from .continuous import ODEFunc, ContinuousFlow
 
 __all__ = ["Flow", "SequentialFlow", "HipFlow", "CouplingLayer", "SplineCouplingLayer",
            "rational_quadratic_spline", "ARQS", "MaskedLinear", "MADE", "MaskedAutoregressiveFlow",
-           "InverseAutoregressiveFlow", "made_degrees", "STATS", "reset_stats", "drop_pack_caches",
+           "InverseAutoregressiveFlow", "made_degrees", "ODEFunc", "ContinuousFlow", "STATS", "reset_stats", "drop_pack_caches",
            "drop_layer_pack_caches"]

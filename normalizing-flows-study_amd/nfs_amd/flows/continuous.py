@@ -1,0 +1,192 @@
+"""Continuous normalizing flow — drop-in for src/flows/continuous/.
+
+  ODEFunc          ode_func.py:4-91      Linear(dim+1, H) -> Tanh -> Linear(H, H) -> Tanh -> Linear(H, dim)
+                                         on [z, t] (time is the LAST input column)
+  ContinuousFlow   continuous_flow.py:6-138
+
+The flow integrates the augmented state [z, l], dz/dt = v(z, t), dl/dt = +tr(dv/dz) (the
+reference's sign, ode_func.py:72-76), from t = 0 to 1 (forward) or 1 to 0 (inverse) with the
+reference's solver settings: torchdiffeq's fixed-grid `rk4` — the 3/8 rule, not the classic
+tableau — at `step_size` 0.01:
+
+    k1 = f(t0, y)
+    k2 = f(t0 + dt/3,  y + dt*k1/3)
+    k3 = f(t0 + 2dt/3, y + dt*(k2 - k1/3))
+    k4 = f(t1,         y + dt*(k1 - k2 + k3))
+    y1 = y + (k1 + 3*(k2 + k3) + k4) * dt * 0.125
+
+on the grid g_k = k*step_size + a, k < n = ceil((b - a)/step_size + 1), g_{n-1} := b (computed in
+the dtype of the times tensor, float32 by default; the last step may be short). A decreasing
+interval integrates the negated-time problem: the same grid walked downward with negative dt.
+Equal times return the input and zeros. After the last step the reference's guards apply
+(continuous_flow.py:65-74): a NaN/Inf output element returns its input element, a NaN/Inf log-det
+becomes 0, both are clamped to [-10, 10]. (Its try/except fall-backs to Euler and to the identity
+are not reproduced: a fixed-step solver does not raise.)
+
+On a ROCm device the whole integration of a call is ONE gfx950 kernel (csrc/nfx_cnf*.hip) for
+dim <= 8 and hidden_dim in {32, 64, 128}; other shapes raise NotImplementedError there (or run the
+composite with ALLOW_TORCH_FALLBACK). Gradients recompute through the torch composite on the GPU.
+"""
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from .flow import HipFlow
+
+
+class ODEFunc(nn.Module):
+    """Time-conditioned velocity field and its divergence (ode_func.py:4-91).
+
+    The divergence is the exact closed-form trace for every `dim`: one forward-mode tangent per
+    input dimension,
+
+        tr = sum_i W3[i, :] . ((1 - h2^2) * (W2 . ((1 - h1^2) * W1[:, i])))
+
+    with h1 = tanh(W1 [z; t] + b1), h2 = tanh(W2 h1 + b2). ONE DELIBERATE DIFFERENCE from the
+    reference: for dim > 2 it switches to a Hutchinson estimate with fresh randn noise per
+    evaluation (ode_func.py:64-70), which is unreproducible by construction; the exact trace is
+    the quantity that estimate targets. For dim <= 2 the two agree."""
+
+    def __init__(self, dim, hidden_dim):
+        super().__init__()
+        self.dim = dim
+        self.net = nn.Sequential(
+            nn.Linear(dim + 1, hidden_dim),
+            nn.Tanh(),
+            nn.Linear(hidden_dim, hidden_dim),
+            nn.Tanh(),
+            nn.Linear(hidden_dim, dim),
+        )
+        self._initialize_weights()
+
+    def _initialize_weights(self):
+        """ode_func.py:79-91: Xavier-normal weights, zero biases, zero final layer (a fresh flow is
+        the identity with zero log-det). Same order as the reference, so seeded inits match."""
+        for layer in self.net:
+            if isinstance(layer, nn.Linear):
+                nn.init.xavier_normal_(layer.weight, gain=1.0)
+                if layer.bias is not None:
+                    nn.init.zeros_(layer.bias)
+        final = self.net[-1]
+        nn.init.zeros_(final.weight)
+        if final.bias is not None:
+            nn.init.zeros_(final.bias)
+
+    def linears(self):
+        return [self.net[0], self.net[2], self.net[4]]
+
+    def velocity_and_trace(self, t, z):
+        """(v(z, t) [B, dim], tr(dv/dz) [B]) in z's dtype; t is a 0-d tensor or a float."""
+        l1, l2, l3 = self.linears()
+        d = self.dim
+        w1, w2, w3 = (l.weight.to(z.dtype) for l in (l1, l2, l3))
+        b1, b2, b3 = (l.bias.to(z.dtype) for l in (l1, l2, l3))
+        t_col = torch.as_tensor(t, dtype=z.dtype, device=z.device).expand(z.shape[0]).unsqueeze(1)
+        h1 = torch.tanh(torch.cat([z, t_col], dim=1) @ w1.t() + b1)
+        h2 = torch.tanh(h1 @ w2.t() + b2)
+        v = h2 @ w3.t() + b3
+        t1 = (1 - h1 * h1).unsqueeze(1) * w1[:, :d].t().unsqueeze(0)   # [B, d, H]: d h1 / d z_i
+        u = (1 - h2 * h2).unsqueeze(1) * (t1 @ w2.t())                  # [B, d, H]: d h2 / d z_i
+        tr = (u * w3.unsqueeze(0)).sum(dim=(1, 2))
+        return v, tr
+
+    def forward(self, t, augmented_state):
+        """d/dt of [z, log_det] (ode_func.py:30-77)."""
+        v, tr = self.velocity_and_trace(t, augmented_state[:, :self.dim])
+        return torch.cat([v, tr.unsqueeze(1)], dim=1)
+
+
+class ContinuousFlow(HipFlow):
+    """Continuous normalizing flow (continuous_flow.py:6-138) with the exact divergence for every
+    `dim` (see ODEFunc for that one deliberate difference from the reference)."""
+
+    step_size = 0.01  # options={'step_size': 0.01}; a class attribute, the signature stays the reference's
+
+    def __init__(self, dim, hidden_dim=64):
+        super().__init__()
+        self.data_dim = dim
+        self.dim = dim
+        self.ode_func = ODEFunc(dim, hidden_dim)
+
+    @property
+    def hidden_dim(self):
+        return self.ode_func.net[0].out_features
+
+    def forward(self, z, integration_times=None):
+        """Sampling direction: t from 0 to 1 (or integration_times = [a, b])."""
+        return self._dispatch(z, 1 if integration_times is None else self._times(integration_times))
+
+    def inverse(self, x, integration_times=None):
+        """Density direction: t from 1 to 0 (or integration_times = [a, b])."""
+        return self._dispatch(x, -1 if integration_times is None else self._times(integration_times))
+
+    # `direction` is +1, -1 or a times tensor [a, b]; it travels unchanged through HipFlow's routing
+    # and the autograd recompute.
+    @staticmethod
+    def _times(direction):
+        if isinstance(direction, int):
+            return torch.tensor([0.0, 1.0] if direction > 0 else [1.0, 0.0])
+        t = torch.as_tensor(direction).detach().cpu()
+        if not t.is_floating_point():
+            t = t.float()
+        if t.numel() != 2:
+            raise ValueError("integration_times must hold two times [t_begin, t_end]")
+        return t.reshape(2)
+
+    def time_grid(self, times):
+        """(t_k [n], in the dtype of `times`): the solver's grid from times[0] to times[1]."""
+        a, b = times[0], times[1]
+        sgn = 1.0 if bool(a <= b) else -1.0
+        s0, s1 = a * sgn, b * sgn
+        step = torch.tensor(self.step_size, dtype=times.dtype)
+        n = int(torch.ceil((s1 - s0) / step + 1))
+        grid = torch.arange(n, dtype=times.dtype) * step + s0
+        grid[-1] = s1
+        return grid * sgn
+
+    def _torch_call(self, x, direction):
+        """The scheme, literally, in x's dtype (CPU tensors, float64, the autograd recompute)."""
+        times = self._times(direction)
+        if bool(times[0] == times[1]):
+            return x, torch.zeros(x.shape[0], device=x.device, dtype=x.dtype)
+        grid = self.time_grid(times).to(device=x.device, dtype=x.dtype).unbind(0)
+        f = self.ode_func.velocity_and_trace
+        y, ld = x, torch.zeros(x.shape[0], device=x.device, dtype=x.dtype)
+        for t0, t1 in zip(grid[:-1], grid[1:]):
+            dt = t1 - t0
+            k1, l1 = f(t0, y)
+            k2, l2 = f(t0 + dt / 3, y + dt * k1 / 3)
+            k3, l3 = f(t0 + 2 * dt / 3, y + dt * (k2 - k1 / 3))
+            k4, l4 = f(t1, y + dt * (k1 - k2 + k3))
+            y = y + (k1 + 3 * (k2 + k3) + k4) * dt * 0.125
+            ld = ld + (l1 + 3 * (l2 + l3) + l4) * dt * 0.125
+        y = torch.where(torch.isnan(y) | torch.isinf(y), x, y)
+        ld = torch.where(torch.isnan(ld) | torch.isinf(ld), torch.zeros_like(ld), ld)
+        return torch.clamp(y, min=-10.0, max=10.0), torch.clamp(ld, min=-10.0, max=10.0)
+
+    # -- gfx950 path -------------------------------------------------------------------------------
+    def _hip_supported(self, x):
+        if x.dim() != 2 or x.shape[1] != self.dim:
+            return False, f"input shape {tuple(x.shape)} vs dim={self.dim}"
+        if not _lib.lib().nfx_cnf_supported(max(x.shape[0], 1), self.dim, self.hidden_dim):  # (B = 0: a no-op)
+            return False, (f"dim={self.dim} hidden_dim={self.hidden_dim} outside the kernel family "
+                           f"(dim <= 8, hidden_dim in {{32, 64, 128}})")
+        return True, ""
+
+    def _build_pack(self, device):
+        L = _lib.lib()
+        d, H = self.dim, self.hidden_dim
+        packed = torch.empty(L.nfx_cnf_packed_floats(d, H), device=device, dtype=torch.float32)
+        t = [p.detach().to(device=device, dtype=torch.float32).contiguous()
+             for lin in self.ode_func.linears() for p in (lin.weight, lin.bias)]
+        _lib.check(L.nfx_cnf_pack(*[_lib.ptr(p) for p in t], d, H, _lib.ptr(packed), _lib.stream_of(packed)),
+                   "nfx_cnf_pack")
+        return packed
+
+    def _hip_launch(self, x, out, log_det, direction, accumulate):
+        packed = self._packed(x.device, self._build_pack)
+        times = self._times(direction).float()
+        _lib.check(_lib.lib().nfx_cnf_integrate(
+            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), x.shape[0], self.dim,
+            self.hidden_dim, float(times[0]), float(times[1]), float(torch.tensor(self.step_size)),
+            int(bool(accumulate)), _lib.stream_of(x)), "nfx_cnf_integrate")
