@@ -1,6 +1,7 @@
 // Affine-coupling kernel template (see nfx_affine.hip for the design notes).
 #pragma once
 #include <type_traits>
+#include <utility>
 
 #include "nfx_common.h"
 
@@ -25,7 +26,7 @@ struct AffineLayout {
 };
 
 // Split tail (d <= 8, H <= 64), appended to the image and derived from it on device
-// (nfx_affine_split_pack): what affine_net_split reads, contiguous so that a kernel stages only
+// (nfx_affine_split_pack): what affine_nets_split_pipe reads, contiguous so that a kernel stages only
 // this region into LDS. Per net: w1 b1 b2 w3 b3 (copies, the fp32 formats above) and W2 as three
 // bf16 pieces W2 ~ W2_0 + W2_1 + W2_2 (round-to-nearest split, split_block) in v_mfma_f32_32x32x16_bf16
 // A-operand order [out tile][k block][piece][lane][4 dwords]; then the mask and two safety words:
@@ -236,7 +237,226 @@ __device__ __forceinline__ void split_block(const f32x16& a, int half, u32x4 (&x
     }
 }
 
-// Conditioner MLP of one net on the split tail S (LDS) for a 64-sample chunk (TILES = 2) or a
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), expanded by the front end.
+template <class F, int... I>
+__device__ __forceinline__ void static_for_seq(F&& f, std::integer_sequence<int, I...>) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_seq(f, std::make_integer_sequence<int, N>{});
+}
+
+// Piece products of one k block, in accumulation order: W2 piece, activation piece. All but the
+// last (the big product w0 x0, into the bias-initialised hi) accumulate into lo; hi + lo is
+// added once per output tile, so the running sum takes only 2 HT MFMA roundings instead of 6 per
+// k block.
+#if NFX_SPLIT_TERMS == 8
+constexpr int kSplitTermW[8] = {2, 1, 2, 1, 0, 1, 0, 0}, kSplitTermX[8] = {1, 2, 0, 1, 2, 0, 1, 0};
+#else
+constexpr int kSplitTermW[6] = {2, 1, 0, 1, 0, 0}, kSplitTermX[6] = {0, 1, 2, 0, 1, 0};
+#endif
+
+// Both conditioner MLPs of a unit on the split tail S (LDS) for a 64-sample chunk (TILES = 2) or
+// a 32-sample half chunk (TILES = 1): sv / bv = clamp(net(x*m), -10, 10)[j] of the s and b nets
+// for the lane's sample, as affine_net.
+//
+// One software pipeline over the 2 TILES stages (net, sample tile) x 2 HT k blocks. A k block is
+// NFX_SPLIT_TERMS * HT MFMAs: its three activation pieces xp against the three W2 pieces of both
+// output tiles (k block outer, so xp dies after one block; the output tiles alternate, so
+// consecutive MFMAs are independent; every accumulator still takes its products in the order of
+// the straight loop: k block by k block, the terms of kSplitTerm in turn). A
+// v_mfma_f32_32x32x16_bf16 holds the SIMD's vector issue for 8 of its 32 cycles, so the vector
+// work goes INTO the gaps between a block's MFMAs, a few instructions each, pinned there by
+// sched_barriers (left to itself the scheduler clusters the MFMAs in runs of 24 with blocks of
+// 60-230 vector instructions between them, and the two pipes take turns):
+//   * the layer-1 ReLU and 3-piece split of the NEXT k block (of the next stage at a stage's
+//     last block), 12 slots of 3-6 instructions, each two independent chains;
+//   * the fold of the PREVIOUS stage's finished output tiles (hi + lo, ReLU, the W3 fmas), two
+//     accumulator registers (2 (2 + D) instructions) at a time, spread evenly over the stage.
+//     The adds are scalar: a vector hi + lo becomes v_pk_add_f32, which the hardware guide
+//     prices above its issue slot beside MFMAs, and the packed form spilled when tried
+//     (DESIGN.md). Not inline asm either: the hazard recognizer does not see an asm operand that
+//     reads an MFMA result;
+//   * the LDS reads: the next block's W2 pieces, this stage's layer-2 bias, the W3 quads two
+//     gaps ahead of their fold items; and layer 1 of the next stage (fp32 MFMAs) two blocks ahead
+//     of its first split.
+// Only the first block's split and the last stage's fold run outside an MFMA's shadow. At
+// HT = 2, d = 2 a gap carries 4-8 vector instructions and at most 2 LDS reads; the stage's peak
+// is ~230 live VGPRs (two stages' accumulators while the fold drains, 128; the next stage's layer
+// 1, 32; two blocks' operands, 72), hence 8 waves per workgroup (2 per SIMD) in the streaming
+// chain, the only caller (affine_nets_split<..., PIPE = true>).
+template <int HT, int D, int TILES>
+__device__ __forceinline__ void affine_nets_split_pipe(const float* __restrict__ S, const AffineSplit& SL,
+                                                       const float (&xb)[2][(D + 1) / 2], float (&sv)[D],
+                                                       float (&bv)[D]) {
+    constexpr int KS1 = (D + 1) / 2;
+    constexpr int NS = 2 * TILES;             // stages: net s / TILES, sample tile s % TILES
+    constexpr int KB = 2 * HT;                // k blocks per stage
+    constexpr int NT = NFX_SPLIT_TERMS;
+    constexpr int NM = NT * HT;               // MFMAs (gaps) per block
+    constexpr int NG = KB * NM;               // gaps per stage
+    constexpr int NFI = 16 * HT;              // fold items per stage
+    constexpr int NQ = 3 * HT;                // W2 quads per block
+    constexpr int WG0 = (NM - NQ) / 2;        // gap of a block that reads the next block's first W2 quad
+    constexpr int L1G = (KB - 2) * NM;        // gap of a stage that runs layer 1 of the next stage
+    constexpr int L1P = L1G >= 2 ? L1G - 2 : 0;  // ... and the gap that reads its bias
+    constexpr int HB0 = NM / 2;               // gap of a stage's first block that reads the first layer-2 bias
+    const int lane = lane_id(), h = lane >> 5;
+
+    const float* Sn[NS];        // the stage's net image (an opaque copy per stage: no reads merged
+    const u32x4* w2n[NS];       // across stages into a register cache of W2 or of the biases)
+    f32x16 h1[NS][HT];          // layer 1 of the stage's tile, before the ReLU
+    uint32_t u[NS * KB][3][8];  // pieces of a block's 8 activations
+    u32x4 xp[NS * KB][3];       // ... packed: the block's B operands
+    u32x4 w[NS * KB][HT][3];    // the block's A operands
+    f32x16 hi[NS][HT], lo[NS][HT];
+    f32x4 w3q[NS][HT][D][4];
+    float r1[NS * KB][8], tf[NS][NFI];
+    float part[2][D][2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int j = 0; j < D; ++j) part[n][j][0] = part[n][j][1] = 0.f;
+
+    auto base = [&](int s) __attribute__((always_inline)) {
+        Sn[s] = S + (s / TILES) * SL.net + opaque_zero();
+        w2n[s] = reinterpret_cast<const u32x4*>(Sn[s] + SL.w2s) + lane;
+    };
+    auto l1_bias = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht) h1[s][ht] = load_bias16(Sn[s] + SL.b1 + ht * 32, h);
+    };
+    auto l1_mfma = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ht = 0; ht < HT; ++ht)
+#pragma unroll
+            for (int ks = 0; ks < KS1; ++ks)
+                h1[s][ht] = mfma32(Sn[s][SL.w1 + (ht * KS1 + ks) * 64 + lane], xb[s % TILES][ks], h1[s][ht]);
+    };
+    // slot i of block b's split (split3 and split_block, cut into slots that each hold two
+    // independent dependency chains): slot 3q: ReLU, first piece and remainder of activations 2q,
+    // 2q + 1; slot 3q + 1: their second and third pieces; slot 3q + 2: the three packs of q
+    auto split_slot = [&](int b, int i) __attribute__((always_inline)) {
+        const int s = b / KB, kb = b % KB, q = i / 3;
+#pragma unroll
+        for (int e = 2 * q; e < 2 * q + 2; ++e) {
+            if (i % 3 == 0) {
+                const float x = trelu(h1[s][kb >> 1][8 * (kb & 1) + e]);
+                u[b][0][e] = __float_as_uint(x) & 0xffff0000u;
+                r1[b][e] = x - __uint_as_float(u[b][0][e]);
+            } else if (i % 3 == 1) {
+                u[b][1][e] = __float_as_uint(r1[b][e]) & 0xffff0000u;
+                u[b][2][e] = __float_as_uint(r1[b][e] - __uint_as_float(u[b][1][e]));
+            }
+        }
+        if (i % 3 == 2) {
+#pragma unroll
+            for (int p = 0; p < 3; ++p) xp[b][p][q] = pack_bf16(u[b][p][2 * q], u[b][p][2 * q + 1]);
+        }
+    };
+    auto w2_quad = [&](int b, int i) __attribute__((always_inline)) {  // in order of first use: piece 2, 1, 0 of every output tile
+        const int s = b / KB, kb = b % KB, p = 2 - i / HT, hto = i % HT;
+        w[b][hto][p] = w2n[s][((hto * KB + kb) * 3 + p) * 64];
+    };
+    auto w3_quads = [&](int s, int hto, int rq) __attribute__((always_inline)) {
+#pragma unroll
+        for (int j = 0; j < D; ++j)
+            w3q[s][hto][j][rq] = *reinterpret_cast<const f32x4*>(Sn[s] + SL.w3 + (j * HT + hto) * 32 + 16 * h + 4 * rq);
+    };
+    auto fold_relu = [&](int s, int f) __attribute__((always_inline)) {
+        tf[s][f] = trelu(hi[s][f / 16][f % 16] + lo[s][f / 16][f % 16]);
+    };
+    auto fold_fma = [&](int s, int f) __attribute__((always_inline)) {
+        const int hto = f / 16, r = f % 16;
+#pragma unroll
+        for (int j = 0; j < D; ++j)
+            part[s / TILES][j][s % TILES] = fmaf(w3q[s][hto][j][r / 4][r % 4], tf[s][f], part[s / TILES][j][s % TILES]);
+    };
+    // the gap of the following stage in which the fmas of fold item f run, together with its
+    // pair's (f ^ 1; the pair's adds and ReLUs one gap earlier): the pairs spread evenly over the
+    // stage; and the gap that reads its W3 quad
+    constexpr auto fold_gap = [](int f) { return (((f | 1) + 1) * NG + NFI - 1) / NFI - 1; };
+    constexpr auto w3_gap = [](int f) {
+        const int g = (((f | 1) + 1) * NG + NFI - 1) / NFI - 1;
+        return g >= 2 ? g - 2 : 0;
+    };
+    // the schedule checks itself for any HT / NFX_SPLIT_TERMS: every fold item runs inside the
+    // following stage, after its add + ReLU gap and its W3 read; the reads of a block fit the block
+    static_assert(fold_gap(NFI - 1) < NG && fold_gap(0) >= 1 && w3_gap(0) < fold_gap(0), "fold schedule");
+    static_assert(WG0 >= 0 && WG0 + NQ <= NM && HB0 + HT <= NM - HT, "read schedule");
+    static_assert(KB < 2 || L1G <= (KB - 1) * NM - 1, "layer 1 of the next stage precedes its first split");
+
+    // prologue: layer 1 of stage 0, block 0's operands
+    base(0);
+    l1_bias(0);
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) w2_quad(0, i);
+    l1_mfma(0);
+#pragma unroll
+    for (int i = 0; i < 12; ++i) split_slot(0, i);
+
+    // (static_for: the front end unrolls; the body is too large for the optimizer's pragma-unroll budget)
+    static_for<NS>([&](auto sc) __attribute__((always_inline)) {
+        constexpr int s = decltype(sc)::value;
+        static_for<NG>([&](auto gc) __attribute__((always_inline)) {
+            constexpr int g = decltype(gc)::value;
+            constexpr int kb = g / NM, m = g % NM, b = s * KB + kb;
+            constexpr int t = m / HT, hto = m % HT;
+            __builtin_amdgcn_sched_barrier(0);
+            if (t == NT - 1) {
+                hi[s][hto] = mfma_bf16(w[b][hto][kSplitTermW[t]], xp[b][kSplitTermX[t]], hi[s][hto]);
+            } else {
+                lo[s][hto] = mfma_bf16(w[b][hto][kSplitTermW[t]], xp[b][kSplitTermX[t]],
+                                       kb == 0 && t == 0 ? f32x16{} : lo[s][hto]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            // LDS reads first: they have the rest of the gap, and the following ones, to land
+            if (g == 0 && s + 1 < NS) base(s + 1);
+            if (b + 1 < NS * KB && m >= WG0 && m < WG0 + NQ) w2_quad(b + 1, m - WG0);
+            if (kb == 0 && m >= HB0 && m < HB0 + HT)  // (hi is first used by the block's last term)
+                hi[s][m - HB0] = load_bias16(Sn[s] + SL.b2 + (m - HB0) * 32, h);
+            if (s > 0) {
+#pragma unroll
+                for (int fq = 0; fq < NFI; fq += 4)
+                    if (w3_gap(fq) == g) w3_quads(s - 1, fq / 16, (fq % 16) / 4);
+            }
+            if (s + 1 < NS && g == L1P) l1_bias(s + 1);
+            if (s + 1 < NS && g == L1G) l1_mfma(s + 1);
+            // vector work: the next block's split, the previous stage's fold
+            if (b + 1 < NS * KB) {
+#pragma unroll
+                for (int i = m * 12 / NM; i < (m + 1) * 12 / NM; ++i) split_slot(b + 1, i);
+            }
+            if (s > 0) {
+#pragma unroll
+                for (int f = 0; f < NFI; ++f)
+                    if ((fold_gap(f) >= 1 ? fold_gap(f) - 1 : 0) == g) fold_relu(s - 1, f);
+#pragma unroll
+                for (int f = 0; f < NFI; ++f)
+                    if (fold_gap(f) == g) fold_fma(s - 1, f);
+            }
+        });
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    // epilogue: the last stage's fold
+#pragma unroll
+    for (int fq = 0; fq < NFI; fq += 4) w3_quads(NS - 1, fq / 16, (fq % 16) / 4);
+#pragma unroll
+    for (int f = 0; f < NFI; ++f) {
+        fold_relu(NS - 1, f);
+        fold_fma(NS - 1, f);
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+        sv[j] = tclamp(halves_sum(part[0][j][0], part[0][j][1]) + Sn[0][SL.b3 + j], -10.f, 10.f);
+        bv[j] = tclamp(halves_sum(part[1][j][0], part[1][j][1]) + Sn[NS - 1][SL.b3 + j], -10.f, 10.f);
+    }
+}
+
+// The straight (not pipelined) form, which the per-layer kernel and the chain shapes outside
+// affine_split_piped run: the conditioner
+// MLP of one net on the split tail S (LDS) for a 64-sample chunk (TILES = 2) or a
 // 32-sample half chunk. Returns clamp(net(x*m), -10, 10)[j] for the lane's sample, as affine_net.
 template <int HT, int D, int TILES = 2>
 __device__ __forceinline__ void affine_net_split(const float* __restrict__ S, const AffineSplit& SL,
@@ -312,13 +532,19 @@ __device__ __forceinline__ void affine_net_split(const float* __restrict__ S, co
         res[j] = tclamp(halves_sum(part[j][0], part[j][1]) + S[SL.b3 + j], -10.f, 10.f);
 }
 
+// Chain shapes whose split nets run the software pipeline: H = 64 at d = 2 and 4, where it
+// measured a gain at 1M rows and at a 125k shard. The H = 32 chains measured inside
+// the noise either way and keep the straight nets; d = 8 at H = 64 overflows 256 VGPRs piped
+// (229-242 spilled; 0.95 ms against 0.64 for a 4-layer chain at 1M rows).
+__host__ __device__ constexpr bool affine_split_piped(int HT, int D) { return HT == 2 && D <= 4; }
+
 // Both conditioner nets of a unit: the split nets from the staged tail S, and — only when a
 // 32-row sample tile has a masked input beyond xsafe (non-finite or huge; NaN fails the test) or
 // the layer's W2 is unsafe — the fp32 nets (affine_net) from the layer's fp32 image Pg in global
 // memory, whose results replace the split ones on that tile's lanes (lane l holds sample
 // ub + l: tile l >> 5). The choice is per 32-aligned tile, so a row's bits never depend on
 // rows outside its tile.
-template <int HT, int D, int TILES>
+template <int HT, int D, int TILES, bool PIPE>
 __device__ __forceinline__ void affine_nets_split(const float* __restrict__ S, const AffineSplit& SL,
                                                   const float* __restrict__ Pg, const AffineLayout& L,
                                                   const float (&xb)[2][(D + 1) / 2], float (&sv)[D], float (&bv)[D]) {
@@ -333,9 +559,13 @@ __device__ __forceinline__ void affine_nets_split(const float* __restrict__ S, c
         for (int ks = 0; ks < KS1; ++ks) bad = bad || !(fabsf(xb[st][ks]) <= xs);
         fast[st] = wok && __builtin_amdgcn_ballot_w64(bad) == 0;
     }
-    affine_net_split<HT, D, TILES>(S, SL, xb, sv);
-    __builtin_amdgcn_sched_barrier(0);  // one net's activations live at a time
-    affine_net_split<HT, D, TILES>(S + SL.net, SL, xb, bv);
+    if constexpr (PIPE) {
+        affine_nets_split_pipe<HT, D, TILES>(S, SL, xb, sv, bv);
+    } else {
+        affine_net_split<HT, D, TILES>(S, SL, xb, sv);
+        __builtin_amdgcn_sched_barrier(0);  // one net's activations live at a time
+        affine_net_split<HT, D, TILES>(S + SL.net, SL, xb, bv);
+    }
     if (!(fast[0] && (TILES == 1 || fast[1]))) {
         __builtin_amdgcn_sched_barrier(0);
         const float* P = Pg + opaque_zero();  // (no hoisted global addresses for this rare path)
@@ -362,7 +592,7 @@ __global__ __launch_bounds__(256) void affine_coupling_kernel(
     float* __restrict__ logp, double* __restrict__ partials, double* __restrict__ sums, float cgauss) {
     constexpr AffineLayout L = affine_layout(D, HT);
     constexpr int KS1 = L.KS1;
-    // H <= 64: only the split tail is staged (layer 2 on the split bf16 MFMAs, affine_net_split)
+    // H <= 64: only the split tail is staged (layer 2 on the split bf16 MFMAs, affine_nets_split_pipe)
     constexpr bool SPLIT = affine_has_split(D, HT);
     constexpr AffineSplit SL = affine_split(D, HT);
     constexpr int MASK = SPLIT ? SL.mask : L.mask;
@@ -439,7 +669,9 @@ __global__ __launch_bounds__(256) void affine_coupling_kernel(
 
         float sv[D], bv[D];
         if constexpr (SPLIT) {
-            affine_nets_split<HT, D, TILES>(smi, SL, packed, L, xb, sv, bv);
+            // (the straight nets: this kernel's grid is sized by occupancy, 2-3 waves per SIMD at
+            // 168-233 VGPRs; the pipeline's 256 would leave one)
+            affine_nets_split<HT, D, TILES, false>(smi, SL, packed, L, xb, sv, bv);
         } else {
             affine_net<HT, D, TILES>(smi, L, xb, sv);
             affine_net<HT, D, TILES>(smi + L.net, L, xb, bv);

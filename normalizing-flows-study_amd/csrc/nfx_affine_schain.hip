@@ -124,7 +124,7 @@ __global__ __launch_bounds__(64 * NW) void affine_schain_kernel(
                 }
                 const float* Wi = W + opaque_zero();
                 float sv[D], bv[D];
-                affine_nets_split<HT, D, TILES>(Wi, SL, Pg, L, xb, sv, bv);
+                affine_nets_split<HT, D, TILES, affine_split_piped(HT, D)>(Wi, SL, Pg, L, xb, sv, bv);
                 if (act) {
 #pragma clang fp contract(off)  // separate mul/add roundings, as affine_coupling_kernel / the reference
                     float y[D];
@@ -179,13 +179,16 @@ typedef void (*schain_t)(NfxChainPacks, int, const float*, float*, float*, int64
                          double*, double*, float);
 
 // Waves per workgroup: one workgroup per CU (its LDS holds two weight images + the row slice),
-// 3 waves per SIMD as the per-layer kernel runs (<= 168 VGPRs).
-constexpr int kSchainWaves = 12;
+// 3 waves per SIMD as the per-layer kernel runs (<= 168 VGPRs) with the straight nets; 2 where
+// the split nets run as the software pipeline (affine_split_piped), which overlaps the vector
+// work with the MFMAs inside a wave and needs the 256-VGPR budget for it.
+__host__ __device__ constexpr int schain_waves(int HT, int D) { return affine_split_piped(HT, D) ? 8 : 12; }
 
 template <int HT, int D>
 static schain_t schain_pick_d(int dir, bool logp) {
-    if (dir > 0) return affine_schain_kernel<HT, D, 1, false, kSchainWaves>;
-    return logp ? affine_schain_kernel<HT, D, -1, true, kSchainWaves> : affine_schain_kernel<HT, D, -1, false, kSchainWaves>;
+    constexpr int NW = schain_waves(HT, D);
+    if (dir > 0) return affine_schain_kernel<HT, D, 1, false, NW>;
+    return logp ? affine_schain_kernel<HT, D, -1, true, NW> : affine_schain_kernel<HT, D, -1, false, NW>;
 }
 
 static schain_t schain_pick(int HT, int D, int dir, bool logp) {
@@ -232,7 +235,7 @@ int schain_launch(const NfxChainPacks& P, int nl, const float* in, float* out, f
     const size_t lds = (2 * (size_t)schain_wpad_rt(HT, d) + (size_t)slice * 64 * (d + 1)) * sizeof(float);
     int rc = prepare_lds((const void*)k, lds);
     if (rc) return rc;
-    k<<<(unsigned)grid, 64 * kSchainWaves, lds, s>>>(P, nl, in, out, log_det, B, accumulate, nchunks, (int)slice,
+    k<<<(unsigned)grid, 64 * schain_waves(HT, d), lds, s>>>(P, nl, in, out, log_det, B, accumulate, nchunks, (int)slice,
                                                       logp, reinterpret_cast<double*>(workspace), sums,
                                                       gauss_const(d));
     return check_launch("affine_schain_kernel");

@@ -37,8 +37,9 @@ for spec0 in "$@"; do
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$d/write" -- \
       python3 "$root/bench.py" --config "$c" "${extra[@]}" --full --steps 3 --warmup 1 --no-cpu --no-secondary \
       > "$d/write.log" 2>&1 || exit $?
-    # MFMA pipe busy cycles, instruction mix and the clock (GRBM_GUI_ACTIVE over the 8 XCDs)
-    timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE \
+    # MFMA pipe busy cycles, the cycles a vector instruction ran beside an MFMA, instruction mix and
+    # the clock (GRBM_GUI_ACTIVE over the 8 XCDs): five counters, one pass
+    timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_VALU_MFMA_COEXEC_CYCLES \
       --output-format csv -d "$d/mfma" -- \
       python3 "$root/bench.py" --config "$c" "${extra[@]}" --full --steps 3 --warmup 1 --no-cpu --no-secondary \
       > "$d/mfma.log" 2>&1 || exit $?

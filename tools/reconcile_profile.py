@@ -129,6 +129,11 @@ def mfma_busy(counter_csv, trace_csv, hot):
            # VALU issue slots used, at 4 cycles per wave instruction (8 for transcendentals: a
            # lower bound) — the pipe of the kernels that issue no MFMA (cfg5i)
            "valu_issue_frac": (ivalu - imfma) * 4 / (N_SIMD * cyc) if cyc else None}
+    if all("SQ_VALU_MFMA_COEXEC_CYCLES" in v for v, _ in rows):
+        # cycles in which a vector instruction executed beside an MFMA, as a share of the MFMA-busy cycles
+        coex = sum(v["SQ_VALU_MFMA_COEXEC_CYCLES"] for v, _ in rows) / n
+        out["pmc_mfma"]["SQ_VALU_MFMA_COEXEC_CYCLES"] = coex
+        out["valu_mfma_coexec_of_busy"] = coex / busy if busy else None
     ds = [d for _, d in rows if d]
     if ds:
         mean_ns = sum(ds) / len(ds)
