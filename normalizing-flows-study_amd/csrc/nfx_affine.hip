@@ -207,23 +207,11 @@ int affine_split_pack(float* packed, int d, int H, hipStream_t s) {
 }
 
 static affine_kernel_t pick_affine(int HT, int d, int dir, bool logp) {
-    switch (HT) {
-        case 1: return affine_pick_ht<1>(d, dir, logp);
-        case 2: return affine_pick_ht<2>(d, dir, logp);
-        case 3: return affine_pick_ht<3>(d, dir, logp);
-        case 4: return affine_pick_ht<4>(d, dir, logp);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) { return affine_pick_ht<HT_()>(d, dir, logp); });
 }
 
 static affine_kernel_t pick_affine_small(int HT, int d, int dir, bool logp) {
-    switch (HT) {
-        case 1: return affine_small_pick_ht<1>(d, dir, logp);
-        case 2: return affine_small_pick_ht<2>(d, dir, logp);
-        case 3: return affine_small_pick_ht<3>(d, dir, logp);
-        case 4: return affine_small_pick_ht<4>(d, dir, logp);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) { return affine_small_pick_ht<HT_()>(d, dir, logp); });
 }
 
 // Kernel choice (nfx_affine_kernel_policy). AUTO compares MFMA "rounds": the streaming kernel
@@ -257,9 +245,7 @@ static int affine_wide_launch(const float* packed, const float* in, float* out, 
     const int HT = (H + 31) / 32;
     if (d > 64 || HT > 4)
         return set_error(NFX_EUNSUPPORTED, "affine_coupling: d=%d H=%d outside the compiled family (d<=64, H<=128)", d, H);
-    affine_wide_t k = HT == 1 ? wide_pick<1>(direction, fused)
-                      : HT == 2 ? wide_pick<2>(direction, fused)
-                      : HT == 3 ? wide_pick<3>(direction, fused) : wide_pick<4>(direction, fused);
+    affine_wide_t k = pick_range<1, 4>(HT, [=](auto HT_) { return wide_pick<HT_()>(direction, fused); });
     if (B == 0) return fused ? gauss_finish(reinterpret_cast<double*>(workspace), 0, sums, 0, stream) : NFX_OK;
     if (!packed || !in || !out || !log_det) return set_error(NFX_EINVAL, "affine_coupling: null pointer");
     if (in == out) return set_error(NFX_EINVAL, "affine_coupling: in and out must not alias");

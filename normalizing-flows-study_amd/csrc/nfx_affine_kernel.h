@@ -871,8 +871,19 @@ __global__ __launch_bounds__(64 * kWideWaves) void affine_wide_kernel(
 typedef void (*affine_kernel_t)(const float*, const float*, float*, float*, int64_t, int, int64_t,
                                 float*, double*, double*, float);
 
+// Defined once per HT, in nfx_affine_h<HT>.hip, as affine_pick<HT>: nullptr for a shape not compiled.
 template <int HT>
 affine_kernel_t affine_pick_ht(int d, int dir, bool logp);
+
+// The family's compiled shapes, listed here only: d = 1..8; forward, inverse, and inverse with the
+// fused log_prob (the forward never fuses it).
+template <int HT>
+affine_kernel_t affine_pick(int d, int dir, bool logp) {
+    return pick_range<1, 8>(d, [=](auto D) -> affine_kernel_t {
+        if (dir > 0) return affine_coupling_kernel<HT, D(), 1, false>;
+        return logp ? affine_coupling_kernel<HT, D(), -1, true> : affine_coupling_kernel<HT, D(), -1, false>;
+    });
+}
 
 // Writes the split tail of an eval image after its fp32 part (no-op without one); same stream.
 int affine_split_pack(float* packed, int d, int H, hipStream_t s);

@@ -177,7 +177,17 @@ __global__ __launch_bounds__(128 * HT) void affine_small_kernel(
     }
 }
 
+// Defined once per HT, in nfx_affine_small_h{12,34}.hip, as affine_small_pick<HT>.
 template <int HT>
 affine_kernel_t affine_small_pick_ht(int d, int dir, bool logp);
+
+// The compiled shapes, listed here only: those of the streaming kernel (affine_pick).
+template <int HT>
+affine_kernel_t affine_small_pick(int d, int dir, bool logp) {
+    return pick_range<1, 8>(d, [=](auto D) -> affine_kernel_t {
+        if (dir > 0) return affine_small_kernel<HT, D(), 1, false>;
+        return logp ? affine_small_kernel<HT, D(), -1, true> : affine_small_kernel<HT, D(), -1, false>;
+    });
+}
 
 }  // namespace nfx

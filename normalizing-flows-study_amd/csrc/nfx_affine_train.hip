@@ -337,11 +337,7 @@ static int pad_d(int d) { return d <= 2 ? 2 : (d <= 4 ? 4 : (d <= 8 ? 8 : 0)); }
 static size_t train_dl_bytes(int64_t B, int D) { return ((size_t)B * 2 * D * sizeof(float) + 255) & ~(size_t)255; }
 
 static affine_trainw_kernel_t pick_trainw(int HT, int D, int stage) {
-    switch (HT) {
-        case 3: return affine_trainw_pick_ht<3>(D, stage);
-        case 4: return affine_trainw_pick_ht<4>(D, stage);
-        default: return nullptr;
-    }
+    return pick_range<3, 4>(HT, [=](auto HT_) { return affine_trainw_pick_ht<HT_()>(D, stage); });
 }
 
 // Workgroups along x of a wide-path pass (deterministic, host-computable: the workspace is
@@ -405,11 +401,7 @@ static int trainw_backward(const float* tpack, const float* x, const float* gy, 
 }
 
 static affine_train_kernel_t pick_train(int HT, int D, int stage) {
-    switch (HT) {
-        case 1: return affine_train_pick_ht<1>(D, stage);
-        case 2: return affine_train_pick_ht<2>(D, stage);
-        default: return nullptr;
-    }
+    return pick_range<1, 2>(HT, [=](auto HT_) { return affine_train_pick_ht<HT_()>(D, stage); });
 }
 
 static int train_check(int d, int H, const char* what) {

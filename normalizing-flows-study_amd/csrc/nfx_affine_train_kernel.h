@@ -940,8 +940,19 @@ typedef void (*affine_train_kernel_t)(const float*, const float*, const float*, 
                                       const double*, const double*, void*, float*, float*, int64_t, int, int,
                                       int64_t);
 
+// Defined once per HT, in nfx_affine_train_h<HT>.hip, as affine_train_pick<HT>.
 template <int HT>
 affine_train_kernel_t affine_train_pick_ht(int D, int stage);
+
+// The compiled shapes, listed here only: padded d = 2, 4, 8 and every TrainStage.
+template <int HT>
+affine_train_kernel_t affine_train_pick(int D, int stage) {
+    return pick_of<2, 4, 8>(D, [=](auto D_) {
+        constexpr int DC = D_();
+        return pick_of<TS_STATS1, TS_STATS2, TS_BWD1, TS_BWD2, TS_BWD3, TS_BWD1K, TS_BWD2K, TS_OUTK>(
+            stage, [](auto S) -> affine_train_kernel_t { return affine_train_kernel<HT, DC, S()>; });
+    });
+}
 
 // LDS bytes of affine_train_kernel<HT, D, stage>
 __host__ __device__ constexpr size_t affine_train_lds(int D, int HT, int stage) {

@@ -586,7 +586,18 @@ __global__ __launch_bounds__(kTWGroups * 4 * 64) void affine_trainw_kernel(
 typedef void (*affine_trainw_kernel_t)(const float*, const float*, const float*, const float*, float*, float*, float*,
                                        const double*, const double*, void*, int64_t, int, int, int64_t);
 
+// Defined once per HT, in nfx_affine_trainw_h<HT>.hip, as affine_trainw_pick<HT>.
 template <int HT>
 affine_trainw_kernel_t affine_trainw_pick_ht(int D, int stage);
+
+// The compiled shapes, listed here only: padded d = 2, 4, 8 and every TrainWStage.
+template <int HT>
+affine_trainw_kernel_t affine_trainw_pick(int D, int stage) {
+    return pick_of<2, 4, 8>(D, [=](auto D_) {
+        constexpr int DC = D_();
+        return pick_of<TW_STATS1, TW_STATS2, TW_OUT, TW_BWD1, TW_BWD2, TW_BWD3>(
+            stage, [](auto S) -> affine_trainw_kernel_t { return affine_trainw_kernel<HT, DC, S()>; });
+    });
+}
 
 }  // namespace nfx

@@ -62,13 +62,7 @@ __global__ void arqs_pack_kernel(NfxMlpRaw net, int d, int H, int K, float* pack
 }
 
 static arqs_kernel_t pick_arqs(int HT, int K, int inverse) {
-    switch (HT) {
-        case 1: return arqs_pick_ht<1>(K, inverse);
-        case 2: return arqs_pick_ht<2>(K, inverse);
-        case 3: return arqs_pick_ht<3>(K, inverse);
-        case 4: return arqs_pick_ht<4>(K, inverse);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) { return arqs_pick_ht<HT_()>(K, inverse); });
 }
 
 }  // namespace nfx

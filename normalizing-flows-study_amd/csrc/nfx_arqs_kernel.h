@@ -179,7 +179,16 @@ __global__ __launch_bounds__(64 * HT) void arqs_kernel(ArqsArgs A) {
 
 typedef void (*arqs_kernel_t)(ArqsArgs);
 
+// Defined once per HT, in nfx_arqs_h{12,34}.hip, as arqs_pick<HT>.
 template <int HT>
 arqs_kernel_t arqs_pick_ht(int K, int inverse);
+
+// The compiled shapes, listed here only: K = 2..11 bins, both directions.
+template <int HT>
+arqs_kernel_t arqs_pick(int K, int inverse) {
+    return pick_range<2, 11>(K, [=](auto K_) -> arqs_kernel_t {
+        return inverse ? arqs_kernel<HT, K_(), true> : arqs_kernel<HT, K_(), false>;
+    });
+}
 
 }  // namespace nfx

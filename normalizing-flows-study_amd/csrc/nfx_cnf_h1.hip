@@ -2,5 +2,5 @@
 #include "nfx_cnf_kernel.h"
 
 namespace nfx {
-NFX_CNF_INSTANTIATE(1)
+template <> cnf_kernel_t cnf_pick_ht<1>(int d) { return cnf_pick<1>(d); }
 }  // namespace nfx

@@ -2,5 +2,5 @@
 #include "nfx_cnf_kernel.h"
 
 namespace nfx {
-NFX_CNF_INSTANTIATE(2)
+template <> cnf_kernel_t cnf_pick_ht<2>(int d) { return cnf_pick<2>(d); }
 }  // namespace nfx

@@ -2,5 +2,5 @@
 #include "nfx_cnf_kernel.h"
 
 namespace nfx {
-NFX_CNF_INSTANTIATE(4)
+template <> cnf_kernel_t cnf_pick_ht<4>(int d) { return cnf_pick<4>(d); }
 }  // namespace nfx

@@ -253,24 +253,14 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
 
 typedef void (*cnf_kernel_t)(CnfArgs);
 
-// One translation unit per hidden width (nfx_cnf_h{1,2,4}.hip).
+// Defined once per hidden width, in nfx_cnf_h{1,2,4}.hip, as cnf_pick<HT>.
 template <int HT>
 cnf_kernel_t cnf_pick_ht(int d);
 
-#define NFX_CNF_INSTANTIATE(HT)                                   \
-    template <>                                                   \
-    cnf_kernel_t cnf_pick_ht<HT>(int d) {                         \
-        switch (d) {                                              \
-            case 1: return cnf_kernel<HT, 1>;                     \
-            case 2: return cnf_kernel<HT, 2>;                     \
-            case 3: return cnf_kernel<HT, 3>;                     \
-            case 4: return cnf_kernel<HT, 4>;                     \
-            case 5: return cnf_kernel<HT, 5>;                     \
-            case 6: return cnf_kernel<HT, 6>;                     \
-            case 7: return cnf_kernel<HT, 7>;                     \
-            case 8: return cnf_kernel<HT, 8>;                     \
-            default: return nullptr;                              \
-        }                                                         \
-    }
+// The compiled shapes, listed here only: d = 1..kCnfMaxD.
+template <int HT>
+cnf_kernel_t cnf_pick(int d) {
+    return pick_range<1, kCnfMaxD>(d, [](auto D) -> cnf_kernel_t { return cnf_kernel<HT, D()>; });
+}
 
 }  // namespace nfx

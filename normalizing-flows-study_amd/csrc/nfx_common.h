@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/nfx.h"
+#include "nfx_pick.h"
 
 namespace nfx {
 

@@ -792,15 +792,11 @@ __global__ __launch_bounds__(256) void spline_elem_bwd_kernel(const float* __res
 
 template <bool BWD>
 static const void* spline_elem_pick(int K, bool inv) {
-#define NFX_SE(k)                                                                                         \
-    case k:                                                                                               \
-        if (BWD) return inv ? (const void*)spline_elem_bwd_kernel<k, true> : (const void*)spline_elem_bwd_kernel<k, false>; \
-        return inv ? (const void*)spline_elem_fwd_kernel<k, true> : (const void*)spline_elem_fwd_kernel<k, false>;
-    switch (K) {
-        NFX_SE(2) NFX_SE(3) NFX_SE(4) NFX_SE(5) NFX_SE(6) NFX_SE(7) NFX_SE(8) NFX_SE(9) NFX_SE(10) NFX_SE(11)
-    }
-#undef NFX_SE
-    return nullptr;
+    return pick_range<kSplineMinK, kSplineMaxK>(K, [=](auto K_) -> const void* {
+        constexpr int KC = K_();
+        if (BWD) return inv ? (const void*)spline_elem_bwd_kernel<KC, true> : (const void*)spline_elem_bwd_kernel<KC, false>;
+        return inv ? (const void*)spline_elem_fwd_kernel<KC, true> : (const void*)spline_elem_fwd_kernel<KC, false>;
+    });
 }
 
 // ---- MADE affine flows, element math -----------------------------------------------------
@@ -1279,14 +1275,9 @@ __global__ __launch_bounds__(256) void arqs_step_kernel(const float* __restrict_
 }
 
 static const void* arqs_step_pick(int K, bool inv) {
-#define NFX_AS(k) \
-    case k:       \
-        return inv ? (const void*)arqs_step_kernel<k, true> : (const void*)arqs_step_kernel<k, false>;
-    switch (K) {
-        NFX_AS(2) NFX_AS(3) NFX_AS(4) NFX_AS(5) NFX_AS(6) NFX_AS(7) NFX_AS(8) NFX_AS(9) NFX_AS(10) NFX_AS(11)
-    }
-#undef NFX_AS
-    return nullptr;
+    return pick_range<2, 11>(K, [=](auto K_) -> const void* {
+        return inv ? (const void*)arqs_step_kernel<K_(), true> : (const void*)arqs_step_kernel<K_(), false>;
+    });
 }
 
 }  // namespace nfx
@@ -1351,11 +1342,8 @@ static int64_t thin_splits(int64_t M, int N, int K) {
 template <bool THIN_X>
 static void thin_wgrad_go(int kt, dim3 grid, hipStream_t s, const float* gy, const float* x, const float* sc, int64_t M,
                           int N, int K, int64_t rchunk, float* pw, float* pb) {
-    switch (kt) {
-#define NFX_THIN(KT) case KT: thin_wgrad_kernel<KT, THIN_X><<<grid, 256, 0, s>>>(gy, x, sc, M, N, K, rchunk, pw, pb); break;
-        NFX_THIN(1) NFX_THIN(2) NFX_THIN(3) NFX_THIN(4) NFX_THIN(5) NFX_THIN(6) NFX_THIN(7) NFX_THIN(8)
-#undef NFX_THIN
-    }
+    auto k = pick_range<1, kThin>(kt, [](auto KT) { return &thin_wgrad_kernel<KT(), THIN_X>; });
+    if (k) k<<<grid, 256, 0, s>>>(gy, x, sc, M, N, K, rchunk, pw, pb);
 }
 
 extern "C" size_t nfx_linear_workspace_bytes(int64_t M, int N, int K) {

@@ -183,33 +183,15 @@ template made_seq_kernel_t made_seq_pick_ht<3>(int);
 template made_seq_kernel_t made_seq_pick_ht<4>(int);
 
 static made_par_kernel_t pick_par(int HT, bool wlds, int variant) {
-    switch (HT) {
-        case 1: return made_pick_ht<1>(wlds, variant);
-        case 2: return made_pick_ht<2>(wlds, variant);
-        case 3: return made_pick_ht<3>(wlds, variant);
-        case 4: return made_pick_ht<4>(wlds, variant);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) { return made_pick_ht<HT_()>(wlds, variant); });
 }
 
 static made_par_kernel_t pick_tile(int HT, bool wlds, int variant, bool logp) {
-    switch (HT) {
-        case 1: return made_tile_pick_ht<1>(wlds, variant, logp);
-        case 2: return made_tile_pick_ht<2>(wlds, variant, logp);
-        case 3: return made_tile_pick_ht<3>(wlds, variant, logp);
-        case 4: return made_tile_pick_ht<4>(wlds, variant, logp);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) { return made_tile_pick_ht<HT_()>(wlds, variant, logp); });
 }
 
 static made_seq_kernel_t pick_seq(int HT, int variant) {
-    switch (HT) {
-        case 1: return made_seq_pick_ht<1>(variant);
-        case 2: return made_seq_pick_ht<2>(variant);
-        case 3: return made_seq_pick_ht<3>(variant);
-        case 4: return made_seq_pick_ht<4>(variant);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) { return made_seq_pick_ht<HT_()>(variant); });
 }
 
 int made_big_launch(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d, int H,
@@ -485,8 +467,8 @@ extern "C" int nfx_made_affine_sample(const float* packed, uint64_t seed, uint64
     const MadeLayout L = made_layout(d, HT);
     const int64_t ntiles = (B + 31) / 32;
     const TileConfig c = tile_config(L, ntiles, false);
-    made_sample_kernel_t k = HT == 1 ? made_tile_sample_pick_ht<1>(c.wlds) : HT == 2 ? made_tile_sample_pick_ht<2>(c.wlds)
-                             : HT == 3 ? made_tile_sample_pick_ht<3>(c.wlds) : made_tile_sample_pick_ht<4>(c.wlds);
+    made_sample_kernel_t k =
+        pick_range<1, 4>(HT, [=](auto HT_) { return made_tile_sample_pick_ht<HT_()>(c.wlds); });  // HT <= 4: checked above
     int rc = prepare_lds((const void*)k, c.lds);
     if (rc) return rc;
     int grid = resident_grid((const void*)k, 64 * c.nw, c.lds, (ntiles + c.nw - 1) / c.nw);

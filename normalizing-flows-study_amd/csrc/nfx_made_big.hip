@@ -320,13 +320,9 @@ static int big_launch_ht(const float* packed, const float* in, float* out, float
 
 int made_big_launch(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d, int H,
                     int variant, int accumulate, hipStream_t s) {
-    switch ((H + 31) / 32) {
-        case 5: return big_launch_ht<5>(packed, in, out, log_det, B, d, H, variant, accumulate, s);
-        case 6: return big_launch_ht<6>(packed, in, out, log_det, B, d, H, variant, accumulate, s);
-        case 7: return big_launch_ht<7>(packed, in, out, log_det, B, d, H, variant, accumulate, s);
-        case 8: return big_launch_ht<8>(packed, in, out, log_det, B, d, H, variant, accumulate, s);
-        default: return set_error(NFX_EUNSUPPORTED, "made_affine: no wide-hidden kernel for H=%d", H);
-    }
+    auto launch = pick_range<5, 8>((H + 31) / 32, [](auto HT_) { return &big_launch_ht<HT_()>; });
+    if (!launch) return set_error(NFX_EUNSUPPORTED, "made_affine: no wide-hidden kernel for H=%d", H);
+    return launch(packed, in, out, log_det, B, d, H, variant, accumulate, s);
 }
 
 }  // namespace nfx

@@ -292,13 +292,7 @@ typedef void (*made_seq_bwd_t)(const float*, const float*, const float*, const f
 
 template <int VAR>
 static made_seq_bwd_t seq_bwd_pick(int HT) {
-    switch (HT) {
-        case 1: return made_seq_bwd_kernel<1, VAR>;
-        case 2: return made_seq_bwd_kernel<2, VAR>;
-        case 3: return made_seq_bwd_kernel<3, VAR>;
-        case 4: return made_seq_bwd_kernel<4, VAR>;
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [](auto HT_) -> made_seq_bwd_t { return made_seq_bwd_kernel<HT_(), VAR>; });
 }
 
 bool made_seqw_bwd_supported(int d, int H);

@@ -173,12 +173,6 @@ int made_pack_seqp(int d, int H, float* packed, hipStream_t s) {
     return check_launch("made_seqp_chunk_kernel");
 }
 
-// instantiation shards (nfx_made_seqp_i*.hip): slots S in [S0, S0 + 3]
-made_seqp_kernel_t made_seqp_pick_1(int HT, int S, int variant, bool logp);
-made_seqp_kernel_t made_seqp_pick_5(int HT, int S, int variant, bool logp);
-made_seqp_kernel_t made_seqp_pick_9(int HT, int S, int variant, bool logp);
-made_seqp_kernel_t made_seqp_pick_13(int HT, int S, int variant, bool logp);
-
 static made_seqp_kernel_t seqp_pick(int HT, int S, int variant, bool logp) {
     if (S >= 1 && S <= 4) return made_seqp_pick_1(HT, S, variant, logp);
     if (S >= 5 && S <= 8) return made_seqp_pick_5(HT, S, variant, logp);

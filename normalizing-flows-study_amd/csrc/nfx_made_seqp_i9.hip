@@ -1,28 +1,8 @@
-// Instantiations of made_seqp_kernel (nfx_made_seqp_kernel.h) for S = 9 .. 12 slots (a shard of
-// nfx_made_seqp.hip's dispatch, split for parallel compilation).
+// made_seqp_kernel for S = 9 .. 12 slots: made_seqp_pick (nfx_made_seqp_kernel.h) lists the forms.
 #include "nfx_made_seqp_kernel.h"
 
 namespace nfx {
-
-template <int HT, int S>
-static made_seqp_kernel_t pick_v(int variant, bool logp) {
-    if (variant == NFX_MAF_FORWARD) return made_seqp_kernel<HT, NFX_MAF_FORWARD, false, S>;
-    return logp ? made_seqp_kernel<HT, NFX_IAF_INVERSE, true, S> : made_seqp_kernel<HT, NFX_IAF_INVERSE, false, S>;
-}
-
-template <int HT>
-static made_seqp_kernel_t pick_s(int S, int variant, bool logp) {
-    switch (S) {
-        case 9: return pick_v<HT, 9>(variant, logp);
-        case 10: return pick_v<HT, 10>(variant, logp);
-        case 11: return pick_v<HT, 11>(variant, logp);
-        case 12: return pick_v<HT, 12>(variant, logp);
-        default: return nullptr;
-    }
-}
-
 made_seqp_kernel_t made_seqp_pick_9(int HT, int S, int variant, bool logp) {
-    return HT == 1 ? pick_s<1>(S, variant, logp) : pick_s<2>(S, variant, logp);
+    return made_seqp_pick<9>(HT, S, variant, logp);
 }
-
 }  // namespace nfx

@@ -398,4 +398,25 @@ __global__ __launch_bounds__(kSeqpThreads) void made_seqp_kernel(
 typedef void (*made_seqp_kernel_t)(const float*, const float*, float*, float*, int64_t, int, int, int, float*,
                                    double*, double*, float);
 
+// Instantiation shards, split for a parallel build: made_seqp_pick_<S0> (nfx_made_seqp_i<S0>.hip) is
+// made_seqp_pick<S0> and serves the slot counts S = S0 .. S0 + 3.
+made_seqp_kernel_t made_seqp_pick_1(int HT, int S, int variant, bool logp);
+made_seqp_kernel_t made_seqp_pick_5(int HT, int S, int variant, bool logp);
+made_seqp_kernel_t made_seqp_pick_9(int HT, int S, int variant, bool logp);
+made_seqp_kernel_t made_seqp_pick_13(int HT, int S, int variant, bool logp);
+
+// The compiled forms, listed here only: MAF forward, IAF inverse, IAF inverse with the fused log_prob.
+template <int HT, int S>
+made_seqp_kernel_t made_seqp_variant(int variant, bool logp) {
+    if (variant == NFX_MAF_FORWARD) return made_seqp_kernel<HT, NFX_MAF_FORWARD, false, S>;
+    return logp ? made_seqp_kernel<HT, NFX_IAF_INVERSE, true, S> : made_seqp_kernel<HT, NFX_IAF_INVERSE, false, S>;
+}
+
+template <int S0>
+made_seqp_kernel_t made_seqp_pick(int HT, int S, int variant, bool logp) {
+    return pick_range<S0, S0 + 3>(S, [=](auto S_) {
+        return HT == 1 ? made_seqp_variant<1, S_()>(variant, logp) : made_seqp_variant<2, S_()>(variant, logp);
+    });
+}
+
 }  // namespace nfx

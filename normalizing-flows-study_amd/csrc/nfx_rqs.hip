@@ -69,56 +69,19 @@ typedef void (*rqs_bwd_kernel_t)(const float*, const float*, const float*, const
 typedef void (*rqs_kernel_t)(const float*, const float*, const float*, const float*, float*, float*,
                              int64_t, float, float, float, float, float);
 
-template <int K>
-static rqs_kernel_t rqs_dir(int inv) {
-    return inv ? rqs_unit_kernel<K, true> : rqs_unit_kernel<K, false>;
-}
-
-template <int K>
-static rqs_bwd_kernel_t rqs_bwd_dir(int inv) {
-    return inv ? rqs_unit_bwd_kernel<K, true> : rqs_unit_bwd_kernel<K, false>;
-}
+// Compiled bin counts of the stand-alone unit spline, both directions.
+constexpr int kRqsMinK = 2, kRqsMaxK = 16;
 
 static rqs_bwd_kernel_t pick_rqs_bwd(int K, int inv) {
-    switch (K) {
-        case 2: return rqs_bwd_dir<2>(inv);
-        case 3: return rqs_bwd_dir<3>(inv);
-        case 4: return rqs_bwd_dir<4>(inv);
-        case 5: return rqs_bwd_dir<5>(inv);
-        case 6: return rqs_bwd_dir<6>(inv);
-        case 7: return rqs_bwd_dir<7>(inv);
-        case 8: return rqs_bwd_dir<8>(inv);
-        case 9: return rqs_bwd_dir<9>(inv);
-        case 10: return rqs_bwd_dir<10>(inv);
-        case 11: return rqs_bwd_dir<11>(inv);
-        case 12: return rqs_bwd_dir<12>(inv);
-        case 13: return rqs_bwd_dir<13>(inv);
-        case 14: return rqs_bwd_dir<14>(inv);
-        case 15: return rqs_bwd_dir<15>(inv);
-        case 16: return rqs_bwd_dir<16>(inv);
-        default: return nullptr;
-    }
+    return pick_range<kRqsMinK, kRqsMaxK>(K, [=](auto K_) -> rqs_bwd_kernel_t {
+        return inv ? rqs_unit_bwd_kernel<K_(), true> : rqs_unit_bwd_kernel<K_(), false>;
+    });
 }
 
 static rqs_kernel_t pick_rqs(int K, int inv) {
-    switch (K) {
-        case 2: return rqs_dir<2>(inv);
-        case 3: return rqs_dir<3>(inv);
-        case 4: return rqs_dir<4>(inv);
-        case 5: return rqs_dir<5>(inv);
-        case 6: return rqs_dir<6>(inv);
-        case 7: return rqs_dir<7>(inv);
-        case 8: return rqs_dir<8>(inv);
-        case 9: return rqs_dir<9>(inv);
-        case 10: return rqs_dir<10>(inv);
-        case 11: return rqs_dir<11>(inv);
-        case 12: return rqs_dir<12>(inv);
-        case 13: return rqs_dir<13>(inv);
-        case 14: return rqs_dir<14>(inv);
-        case 15: return rqs_dir<15>(inv);
-        case 16: return rqs_dir<16>(inv);
-        default: return nullptr;
-    }
+    return pick_range<kRqsMinK, kRqsMaxK>(K, [=](auto K_) -> rqs_kernel_t {
+        return inv ? rqs_unit_kernel<K_(), true> : rqs_unit_kernel<K_(), false>;
+    });
 }
 
 }  // namespace nfx

@@ -68,31 +68,10 @@ __global__ void spline_pack_kernel(NfxMlpRaw net, const float* mask, int d, int 
 }
 
 static spline_kernel_t pick_spline(int HT, int K, int dir, bool logp, int d) {
-    if (d > 8) {
-        switch (HT) {
-            case 1: return spline_wide_pick_ht<1>(K, dir, logp);
-            case 2: return spline_wide_pick_ht<2>(K, dir, logp);
-            case 3: return spline_wide_pick_ht<3>(K, dir, logp);
-            case 4: return spline_wide_pick_ht<4>(K, dir, logp);
-            default: return nullptr;
-        }
-    }
-    if (d == 2) {
-        switch (HT) {
-            case 1: return spline_pick_ht<1, 2>(K, dir, logp);
-            case 2: return spline_pick_ht<2, 2>(K, dir, logp);
-            case 3: return spline_pick_ht<3, 2>(K, dir, logp);
-            case 4: return spline_pick_ht<4, 2>(K, dir, logp);
-            default: return nullptr;
-        }
-    }
-    switch (HT) {
-        case 1: return spline_pick_ht<1, 0>(K, dir, logp);
-        case 2: return spline_pick_ht<2, 0>(K, dir, logp);
-        case 3: return spline_pick_ht<3, 0>(K, dir, logp);
-        case 4: return spline_pick_ht<4, 0>(K, dir, logp);
-        default: return nullptr;
-    }
+    return pick_range<1, 4>(HT, [=](auto HT_) {
+        if (d > 8) return spline_wide_pick_ht<HT_()>(K, dir, logp);
+        return d == 2 ? spline_pick_ht<HT_(), 2>(K, dir, logp) : spline_pick_ht<HT_(), 0>(K, dir, logp);
+    });
 }
 
 }  // namespace nfx

@@ -131,11 +131,7 @@ static int spline_bwd_check(int d, int H, int K, int nt, const char* what) {
 }
 
 static spline_bwd_kernel_t pick_spline_bwd(int HT, int K, int inv) {
-    switch (HT) {
-        case 1: return spline_bwd_pick_ht<1>(K, inv);
-        case 2: return spline_bwd_pick_ht<2>(K, inv);
-        default: return nullptr;
-    }
+    return pick_range<1, 2>(HT, [=](auto HT_) { return spline_bwd_pick_ht<HT_()>(K, inv); });
 }
 
 }  // namespace nfx

@@ -739,11 +739,21 @@ __global__ __launch_bounds__(256) void spline_bwd_kernel(
 typedef void (*spline_bwd_kernel_t)(const float*, const float*, const float*, const float*, float*, float*,
                                     int64_t, int, SplineConsts, int64_t);
 
+// Defined once per HT, in nfx_spline_bwd_h<HT>.hip, as spline_bwd_pick<HT>.
 template <int HT>
 spline_bwd_kernel_t spline_bwd_pick_ht(int K, int inv);
 
 // Transformed-dimension tiles one launch handles (their dW3 accumulators stay in registers).
 constexpr int spline_bwd_ntmax(int HT) { return HT == 1 ? 2 : 1; }
+
+// The compiled shapes: the forward family's K range, both directions.
+template <int HT>
+spline_bwd_kernel_t spline_bwd_pick(int K, int inv) {
+    return pick_range<kSplineMinK, kSplineMaxK>(K, [=](auto K_) -> spline_bwd_kernel_t {
+        constexpr int NTM = spline_bwd_ntmax(HT);
+        return inv ? spline_bwd_kernel<HT, K_(), NTM, true> : spline_bwd_kernel<HT, K_(), NTM, false>;
+    });
+}
 
 __host__ __device__ constexpr size_t spline_bwd_lds(int HT) {
     return (size_t)(spline_bwd_layout(HT, spline_bwd_ntmax(HT)).total + 4 * 32 * kTS + 4 * 32 * 8) * sizeof(float);

@@ -834,9 +834,23 @@ __global__ __launch_bounds__(256, (DS == 2 && HT <= 2) ? 3 : 1) void spline_coup
 typedef void (*spline_kernel_t)(const float*, const float*, float*, float*, int64_t, int,
                                 SplineConsts, int, int64_t, float*, double*, double*, float);
 
-// DS = 0: runtime d <= 8; DS = 2: the d = 2 specialisation (nfx_spline_d2_h*.hip)
+// DS = 0: runtime d <= 8 (nfx_spline_h*.hip); DS = 2: the d = 2 specialisation (nfx_spline_d2_h*.hip).
+// Defined once per (HT, DS), one per translation unit, as spline_pick<HT, DS>.
 template <int HT, int DS>
 spline_kernel_t spline_pick_ht(int K, int dir, bool logp);
+
+// The spline family's compiled shapes, listed here only (the wide, chain and backward kernels take
+// their K range from these two constants): K = 2..11 bins; forward, inverse, and inverse with the
+// fused log_prob (the forward never fuses it).
+constexpr int kSplineMinK = 2, kSplineMaxK = 11;
+
+template <int HT, int DS>
+spline_kernel_t spline_pick(int K, int dir, bool logp) {
+    return pick_range<kSplineMinK, kSplineMaxK>(K, [=](auto K_) -> spline_kernel_t {
+        if (dir > 0) return spline_coupling_kernel<HT, K_(), 1, false, DS>;
+        return logp ? spline_coupling_kernel<HT, K_(), -1, true, DS> : spline_coupling_kernel<HT, K_(), -1, false, DS>;
+    });
+}
 
 
 // ---- wide spline coupling layers (8 < d <= 64) -----------------------------------------------
@@ -983,5 +997,13 @@ __global__ __launch_bounds__(64 * kSplineWideWaves) void spline_wide_kernel(
 // wide kernels (8 < d <= 64), one TU per HT (nfx_spline_w_h*.hip)
 template <int HT>
 spline_kernel_t spline_wide_pick_ht(int K, int dir, bool logp);
+
+template <int HT>
+spline_kernel_t spline_wide_pick(int K, int dir, bool logp) {
+    return pick_range<kSplineMinK, kSplineMaxK>(K, [=](auto K_) -> spline_kernel_t {
+        if (dir > 0) return spline_wide_kernel<HT, K_(), 1, false>;
+        return logp ? spline_wide_kernel<HT, K_(), -1, true> : spline_wide_kernel<HT, K_(), -1, false>;
+    });
+}
 
 }  // namespace nfx

@@ -198,7 +198,23 @@ constexpr int kSplineSchainWaves = 12;
 // leave a third of its waves idle there anyway.
 constexpr int kSplineSchainWavesSmall = 8;
 
+// Defined once per HT, in nfx_spline_schain_h<HT>.hip, as spline_schain_pick<HT>.
 template <int HT>
 spline_schain_t spline_schain_pick_ht(int K, int dir, bool logp, bool small);
+
+// Shapes as spline_pick's, each at both workgroup sizes.
+template <int HT, int K, int NW>
+spline_schain_t spline_schain_dir(int dir, bool logp) {
+    if (dir > 0) return spline_schain_kernel<HT, K, 1, false, NW>;
+    return logp ? spline_schain_kernel<HT, K, -1, true, NW> : spline_schain_kernel<HT, K, -1, false, NW>;
+}
+
+template <int HT>
+spline_schain_t spline_schain_pick(int K, int dir, bool logp, bool small) {
+    return pick_range<kSplineMinK, kSplineMaxK>(K, [=](auto K_) {
+        return small ? spline_schain_dir<HT, K_(), kSplineSchainWavesSmall>(dir, logp)
+                     : spline_schain_dir<HT, K_(), kSplineSchainWaves>(dir, logp);
+    });
+}
 
 }  // namespace nfx

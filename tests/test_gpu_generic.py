@@ -27,6 +27,7 @@ import torch.nn as nn
 import nfs_amd
 import oracle
 from conftest import assert_fp32_parity, fp32_jitter, load_golden, oracle_sd, state_dict_from
+from nfs_amd import _lib
 from nfs_amd.flows import generic as G
 from nfs_amd.flows import spline as _sp
 from nfs_amd.flows.flow import STATS
@@ -46,7 +47,9 @@ def _close(c, c64, conditioning, what):
 @pytest.mark.parametrize("M,K,N", [(1000, 2, 64), (4097, 64, 64), (300, 128, 232), (70001, 128, 128),
                                    (5, 3, 1), (1, 96, 33), (2048, 784, 64),
                                    # the thin weight gradient (min(N, K) <= 8): x thin, gy thin, both
-                                   (100003, 8, 256), (3000, 96, 5), (777, 200, 8), (65, 7, 3)])
+                                   (100003, 8, 256), (3000, 96, 5), (777, 200, 8), (65, 7, 3),
+                                   # its narrowest instantiation, of x thin and of gy thin
+                                   (65, 1, 3), (65, 9, 1)])
 def test_linear_kernels_vs_float64(cuda_device, M, K, N):
     g = torch.Generator().manual_seed(M + K + N)
     lin = nn.Linear(K, N)
@@ -99,12 +102,29 @@ def sd64(sd):
                                         (80, 32, 4, [(i % 3 == 0) * 1.0 for i in range(80)])])
 def test_generic_spline_eval_vs_oracle(cuda_device, d, H, K, mask):
     """Eval beyond the fused eval family (H > 128 or d > 64) runs the any-shape path."""
+    _generic_spline_eval(cuda_device, d, H, K, mask, 1000)
+
+
+def test_generic_spline_eval_bin_count_range(cuda_device):
+    """nfx_spline_elem_forward at both ends of its compiled bin counts (K = 2 and 11; B = 65, d = 3), checked as
+    the eval cases above, and one past the top: K = 12 is refused with NFX_EUNSUPPORTED before any launch."""
+    for K in (2, 11):
+        _generic_spline_eval(cuda_device, 3, 160, K, [1, 0, 1], 65)
+    x, mask = torch.rand(65, 3, device=cuda_device), torch.tensor([1.0, 0.0, 1.0], device=cuda_device)
+    prm, ld = torch.zeros(65, 3, 3 * 12 - 1, device=cuda_device), torch.zeros(65, device=cuda_device)
+    p = _lib.ptr
+    rc = _lib.lib().nfx_spline_elem_forward(p(x), p(prm), p(mask), p(torch.empty_like(x)), p(ld), 65, 3, 12, 5.0,
+                                            1e-3, 1e-3, 1e-3, 1, 0, _lib.stream_of(x))
+    assert rc == _lib.NFX_EUNSUPPORTED
+
+
+def _generic_spline_eval(cuda_device, d, H, K, mask, B):
     torch.manual_seed(d * 100 + H + K)
     layer = nfs_amd.SplineCouplingLayer(d, H, torch.tensor(mask, dtype=torch.float32), num_bins=K)
     with torch.no_grad():
         for p in layer.parameters():
             p.add_(0.1 * torch.randn_like(p))
-    x = torch.randn(1000, d) * 2.5
+    x = torch.randn(B, d) * 2.5
     x[0, 0] = float("nan")
     sd = {k: v.clone() for k, v in layer.state_dict().items()}
     layer = layer.to(cuda_device).eval()
@@ -409,6 +429,31 @@ def test_generic_arqs_eval_vs_oracle(cuda_device, d, H, K):
         yr, lr = oracle.arqs(sd, "", x, direction, K=K)
         assert_y(yg.cpu(), yr, 1e-4)
         assert_ld(lg.cpu(), lr, 1e-3)
+
+
+def test_generic_arqs_bin_count_range(cuda_device):
+    """nfx_arqs_step at both ends of its compiled bin counts (K = 2 and 11; B = 65, d = 3, H = 160: the any-shape
+    path) against the float64 module, and one past the top: K = 12 is refused with NFX_EUNSUPPORTED."""
+    x = torch.rand(65, 3, generator=torch.Generator().manual_seed(3))
+    for K in (2, 11):
+        f = _arqs(3, 160, K, 30 + 160 + K)
+        f64 = copy.deepcopy(f).double().eval()
+        fg = f.to(cuda_device).eval()
+        assert not fg._fused_family()
+        for direction in (1, -1):
+            with torch.no_grad():
+                y64, l64 = (f64.forward if direction > 0 else f64.inverse)(x.double())  # CPU composite
+                STATS["hip"] = STATS["torch"] = 0
+                yg, lg = (fg.forward if direction > 0 else fg.inverse)(x.to(cuda_device))
+            assert STATS["hip"] == 1 and STATS["torch"] == 0, STATS
+            assert_y(yg.cpu(), y64, 1e-4)
+            assert_ld(lg.cpu(), l64, 1e-3)
+    xd = x.to(cuda_device)
+    prm, state, ld = torch.zeros(65, 3, 3 * 12 - 1, device=cuda_device), torch.zeros_like(xd), torch.zeros(65, device=cuda_device)
+    p = _lib.ptr
+    rc = _lib.lib().nfx_arqs_step(p(xd), p(prm), p(state), p(ld), None, None, None, None, 65, 3, 12, 0, 1, 0, 1e-3, 1e-3,
+                                  1e-3, _lib.stream_of(xd))
+    assert rc == _lib.NFX_EUNSUPPORTED
 
 
 @pytest.mark.parametrize("d,H,K,direction", [(2, 32, 8, 1), (2, 32, 8, -1), (4, 64, 5, 1), (4, 64, 5, -1),

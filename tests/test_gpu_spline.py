@@ -290,3 +290,44 @@ def test_rqs_unit_nd_and_unsupported(cuda_device):
         nfs_amd.rational_quadratic_spline(dev[0], *(torch.randn(B, d, k).to(cuda_device) for k in (17, 17, 16)))
     with pytest.raises(ValueError):
         nfs_amd.rational_quadratic_spline(dev[0], dev[1][:1], dev[2], dev[3])
+
+
+def test_rqs_unit_bin_count_range(cuda_device):
+    """nfx_rqs_unit and nfx_rqs_unit_backward at both ends of their compiled bin counts (K = 2 and 16; N = 65,
+    both directions) against the float64 composite, with the tolerances of test_rqs_unit_backward_vs_float64; one
+    past the top (K = 17) both entry points refuse with NFX_EUNSUPPORTED before any launch."""
+    from nfs_amd import _lib
+    from nfs_amd.flows.spline import _rqs_unit_torch
+    N = 65
+
+    def comp(*v, inverse):
+        return _rqs_unit_torch(*v, inverse, 1e-3, 1e-3, 1e-3)
+
+    for K in (2, 16):
+        gen = torch.Generator().manual_seed(100 + K)
+        a32 = [0.02 + 0.96 * torch.rand(N, generator=gen), torch.randn(N, K, generator=gen),
+               torch.randn(N, K, generator=gen), torch.randn(N, K - 1, generator=gen)]
+        wy, wl = torch.randn(N, generator=gen), torch.randn(N, generator=gen)
+        for inverse in (False, True):
+            y64, l64, g64 = _rqs_grads(comp, [a.double() for a in a32], wy.double(), wl.double(), inverse)
+            _, _, g32 = _rqs_grads(comp, a32, wy, wl, inverse)
+            nfs_amd.reset_stats()
+            y, ld, gg = _rqs_grads(nfs_amd.rational_quadratic_spline, [a.to(cuda_device) for a in a32],
+                                   wy.to(cuda_device), wl.to(cuda_device), inverse)
+            assert nfs_amd.STATS["hip"] == 2 and nfs_amd.STATS["torch"] == 0, nfs_amd.STATS
+            assert np.allclose(y.cpu().numpy(), y64.numpy(), rtol=1e-5, atol=1e-5), f"y K={K} inverse={inverse}"
+            assert np.allclose(ld.cpu().numpy(), l64.numpy(), rtol=1e-4, atol=1e-4), f"ld K={K} inverse={inverse}"
+            for name, a, b32, b64 in zip(("dL/dx", "dL/dwidths", "dL/dheights", "dL/dderivatives"), gg, g32, g64):
+                a, b32, b64 = a.double().cpu(), b32.double(), b64.double()
+                bound = 2e-5 * (1 + b64.abs().max().item()) + 4 * (b32 - b64).abs().max().item()
+                err = (a - b64).abs().max().item()
+                assert err <= bound, f"{name} K={K} inverse={inverse}: max err {err:.3g} > {bound:.3g}"
+    K = 17
+    x = torch.rand(N, device=cuda_device)
+    uw, ud = torch.zeros(N, K, device=cuda_device), torch.zeros(N, K - 1, device=cuda_device)
+    out = [torch.empty_like(t) for t in (x, x, uw, uw, ud)]
+    p, L = _lib.ptr, _lib.lib()
+    assert L.nfx_rqs_unit(p(x), p(uw), p(uw), p(ud), p(out[0]), p(out[1]), N, K, 1e-3, 1e-3, 1e-3, 0,
+                          _lib.stream_of(x)) == _lib.NFX_EUNSUPPORTED
+    assert L.nfx_rqs_unit_backward(p(x), p(uw), p(uw), p(ud), p(x), p(x), p(out[0]), p(out[2]), p(out[3]), p(out[4]), N,
+                                   K, 1e-3, 1e-3, 1e-3, 0, _lib.stream_of(x)) == _lib.NFX_EUNSUPPORTED

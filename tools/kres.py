@@ -1,15 +1,18 @@
 """Per-kernel register usage of one translation unit (hipcc -Rpass-analysis=kernel-resource-usage).
     python tools/kres.py normalizing-flows-study_amd/csrc/<file>.hip [extra hipcc flags]"""
+import importlib.util
 import os
 import re
 import subprocess
 import sys
 
 here = os.path.dirname(os.path.abspath(__file__))
-csrc = os.path.join(here, "..", "normalizing-flows-study_amd", "csrc")
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function",
-       f"-I{os.path.join(here, '..', 'include')}", f"-I{csrc}", "-mllvm", "-amdgpu-mfma-vgpr-form=1",
-       "-Rpass-analysis=kernel-resource-usage", "-c", sys.argv[1], "-o", "/tmp/kres.o"] + sys.argv[2:]
+spec = importlib.util.spec_from_file_location(
+    "nfx_build", os.path.join(here, "..", "normalizing-flows-study_amd", "build.py"))
+nfx_build = importlib.util.module_from_spec(spec)
+spec.loader.exec_module(nfx_build)  # the library's own compiler and flags
+cmd = [nfx_build.hipcc()] + nfx_build.CFLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", sys.argv[1],
+                                                 "-o", "/tmp/kres.o"] + sys.argv[2:]
 r = subprocess.run(cmd, capture_output=True, text=True)
 cur = None
 rows = []
