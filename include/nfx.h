@@ -15,7 +15,7 @@
  *     asynchronous; no call synchronises the device, so calls can be captured in a hipGraph.
  *   - Return 0 on success; < 0 on error, with a message in nfx_last_error() (thread-local).
  *     NFX_EINVAL invalid argument, NFX_EUNSUPPORTED shape outside the compiled kernel
- *     family, NFX_ELAUNCH a HIP launch error.
+ *     family, NFX_ELAUNCH a HIP launch error. (Every `int` entry point returns such a status except nfx_abi_version, nfx_*_policy and nfx_*_supported, which return a value.)
  *   - `accumulate` = 0 stores the layer's log|det J| into log_det; 1 adds it in place
  *     (log_det[i] += ld_i), reproducing the sequential float32 accumulation of
  *     NormalizingFlowModel.forward/inverse (src/models/normalizing_flow_model.py:30-65).

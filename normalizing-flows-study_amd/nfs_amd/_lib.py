@@ -1,11 +1,14 @@
 """ctypes binding of libnfx.so (the C-ABI declared in include/nfx.h).
 
 The product path fails loudly when the library is missing: every HIP entry point goes through
-`lib()`, which raises NfxLibraryError instead of silently falling back to eager PyTorch.
+`checked()` / `lib()`, which raise NfxLibraryError instead of silently falling back to eager
+PyTorch. `_SIGNATURES` is the one table of the ABI; `lib()` binds it as plain ctypes (return
+codes), `checked()` as calls that take tensors and raise NfxError on a failing status.
 """
 import ctypes
 import os
 import threading
+import types
 
 import torch
 
@@ -29,41 +32,6 @@ NFX_MADE_SEQ_AUTO = 0
 NFX_MADE_SEQ_SEGMENT = 1
 NFX_MADE_SEQ_WAVE = 2
 NFX_MADE_SEQ_PUSH = 3
-
-# Every symbol include/nfx.h declares (tests check the built library exports all of them).
-EXPORTED_SYMBOLS = (
-    "nfx_abi_version", "nfx_last_error", "nfx_last_kernel", "nfx_debug_fill_lds",
-    "nfx_affine_packed_floats", "nfx_affine_pack", "nfx_affine_coupling", "nfx_affine_coupling_logprob",
-    "nfx_affine_kernel_policy", "nfx_affine_chain", "nfx_affine_chain_logprob", "nfx_affine_chain_supported",
-    "nfx_affine_chain_sample",
-    "nfx_spline_packed_floats", "nfx_spline_pack", "nfx_spline_coupling", "nfx_spline_coupling_logprob",
-    "nfx_spline_chain_supported", "nfx_spline_chain", "nfx_spline_chain_logprob", "nfx_spline_chain_sample",
-    "nfx_rqs_unit", "nfx_rqs_unit_backward",
-    "nfx_arqs_packed_floats", "nfx_arqs_pack", "nfx_arqs",
-    "nfx_made_packed_floats", "nfx_made_pack", "nfx_made_pack_parallel", "nfx_made_pack_sequential", "nfx_made_affine", "nfx_made_affine_logprob", "nfx_made_seq_policy",
-    "nfx_base_normal", "nfx_made_sample_supported", "nfx_made_affine_sample",
-    "nfx_made_pack_backward", "nfx_made_backward_factor_floats", "nfx_made_backward_max_batch",
-    "nfx_made_affine_backward",
-    "nfx_made_seq_backward", "nfx_made_factor_pitch", "nfx_made_param_floats", "nfx_made_wgrad_workspace_bytes", "nfx_made_backward_weights",
-    "nfx_affine_train_pack_floats", "nfx_affine_train_stats_doubles", "nfx_affine_train_grad_doubles",
-    "nfx_affine_train_param_floats", "nfx_affine_train_workspace_bytes", "nfx_affine_train_pack",
-    "nfx_affine_train_stats", "nfx_affine_train_update_running", "nfx_affine_train_backward",
-    "nfx_affine_train_assemble", "nfx_affine_eval_stats", "nfx_affine_train_keep_floats",
-    "nfx_affine_train_stats_keep", "nfx_affine_train_backward_keep", "nfx_affine_train_output", "nfx_affine_train_update_running_counted",
-    "nfx_spline_backward_packed_floats", "nfx_spline_backward_param_floats",
-    "nfx_spline_backward_workspace_bytes", "nfx_spline_pack_backward", "nfx_spline_coupling_backward",
-    "nfx_gauss_workspace_bytes", "nfx_gauss_workspace_init", "nfx_gauss_logprob", "nfx_gauss_logprob_backward",
-    "nfx_flowbn_workspace_bytes", "nfx_flowbn_apply", "nfx_flowbn_moments", "nfx_flowbn_update_running",
-    "nfx_flowbn_backward",
-    "nfx_linear_forward", "nfx_linear_backward_data", "nfx_linear_workspace_bytes", "nfx_linear_backward_weight",
-    "nfx_spline_elem_forward", "nfx_spline_elem_backward", "nfx_spline_elem_forward_bounded",
-    "nfx_spline_elem_backward_bounded", "nfx_spline_rescale", "nfx_arqs_bounds",
-    "nfx_made_elem_forward", "nfx_made_elem_step", "nfx_made_elem_finish", "nfx_made_elem_backward",
-    "nfx_made_elem_seq_backward", "nfx_made_elem_seq_step_backward", "nfx_made_elem_prefix",
-    "nfx_affine_elem_forward", "nfx_affine_elem_backward", "nfx_bn_prepare", "nfx_bn_apply_relu",
-    "nfx_bn_workspace_bytes", "nfx_bn_backward_sums", "nfx_bn_backward_apply", "nfx_arqs_step",
-    "nfx_cnf_packed_floats", "nfx_cnf_pack", "nfx_cnf_supported", "nfx_cnf_integrate",
-)
 
 
 class NfxLibraryError(RuntimeError):
@@ -224,13 +192,46 @@ _SIGNATURES = {
                                    _vp, _vp]),
 }
 
+# Every symbol include/nfx.h declares (tests check the table against the header, type by type,
+# and that the built library exports all of them).
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+# The c_int symbols whose return is a value (a version, a policy, a yes/no), not an NFX_* status;
+# every other c_int symbol returns a status, which the checked handle turns into NfxError.
+_VALUE_RETURNING = frozenset((
+    "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
+    "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_made_sample_supported"))
+
+
+_as_pointer = _vp.from_param  # (an int as a full-width pointer argument, without a c_void_p object)
+
+
+class DevicePtr:
+    """argtype of the checked handle for a `void*`: None (null), anything with .data_ptr() (a
+    tensor), or a plain int (a stream handle, an address the caller already holds)."""
+
+    @staticmethod
+    def from_param(v):
+        # (every launch passes its stream as an int: tested for, an exception would cost ~0.4 us)
+        if v is None or type(v) is int:
+            return _as_pointer(v)
+        return _as_pointer(v.data_ptr())
+
+
+def _raise_on_status(rc, fn, args):
+    if rc != NFX_OK:
+        raise NfxError(f"{fn.__name__} failed (rc={rc}): {lib().nfx_last_error().decode(errors='replace')}")
+    return rc
+
+
 _lock = threading.Lock()
 _lib = None
+_checked = None
 
 
 def load(path=LIB_PATH):
     """Load libnfx.so without touching the GPU (safe on CPU-only hosts)."""
-    global _lib
+    global _lib, _checked
     with _lock:
         if _lib is not None:
             return _lib
@@ -240,19 +241,38 @@ def load(path=LIB_PATH):
                 f"`python normalizing-flows-study_amd/build.py` (or __graft_entry__.build()). "
                 f"The HIP path has no eager fallback.")
         l = ctypes.CDLL(path)
+        n = types.SimpleNamespace()
         for name, (res, args) in _SIGNATURES.items():
             fn = getattr(l, name, None)
             if fn is None:
                 continue
             fn.restype = res
             fn.argtypes = args
+            # a second pointer to the same symbol (getattr would return the raw one again)
+            cf = l._FuncPtr((name, l))
+            cf.__name__ = name
+            cf.restype = res
+            cf.argtypes = [DevicePtr if a is _vp else a for a in args]
+            if res is _int and name not in _VALUE_RETURNING:
+                cf.errcheck = _raise_on_status
+            setattr(n, name, cf)
+        _checked = n
         _lib = l
         return l
 
 
 def lib():
+    """The raw handle: plain ctypes functions, integer return codes, c_void_p arguments."""
     l = _lib
     return l if l is not None else load()
+
+
+def checked():
+    """The checked handle the product path launches through: the same symbols, but pointer
+    arguments take tensors (DevicePtr) and a status other than NFX_OK raises NfxError."""
+    if _checked is None:
+        load()
+    return _checked
 
 
 def available():

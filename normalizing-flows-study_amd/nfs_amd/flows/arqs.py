@@ -129,8 +129,7 @@ class ARQS(HipFlow):
 
     def _map(self, t, bounds, mode):
         out = torch.empty_like(t)
-        _lib.check(_lib.lib().nfx_arqs_bounds(_lib.ptr(t), _lib.ptr(bounds), _lib.ptr(out), t.shape[0], self.dim,
-                                              mode, _lib.stream_of(t)), "nfx_arqs_bounds")
+        _lib.checked().nfx_arqs_bounds(t, bounds, out, t.shape[0], self.dim, mode, _lib.stream_of(t))
         return out
 
     # -- any-shape path (csrc/nfx_generic.hip): the reference's d steps, MADE on MFMA GEMMs --------
@@ -149,11 +148,9 @@ class ARQS(HipFlow):
 
     def _step(self, xr, prm, state, ld, gld, lam, gprm, gx, i, direction, mode):
         B, d = state.shape
-        p = _lib.ptr
-        _lib.check(_lib.lib().nfx_arqs_step(p(xr), p(prm), p(state), p(ld), p(gld), p(lam), p(gprm), p(gx), B, d,
-                                            self.num_bins, i, int(direction), mode, float(self.min_bin_width),
-                                            float(self.min_bin_height), float(self.min_derivative),
-                                            _lib.stream_of(state)), "nfx_arqs_step")
+        _lib.checked().nfx_arqs_step(xr, prm, state, ld, gld, lam, gprm, gx, B, d, self.num_bins, i, int(direction),
+                                     mode, float(self.min_bin_width), float(self.min_bin_height),
+                                     float(self.min_derivative), _lib.stream_of(state))
 
     def _generic_forward_state(self, xr, direction, state=None, ld=None):
         """The reference's d steps (arqs.py:51-78 / :89-112) into `state` (zeroed first) with the
@@ -172,8 +169,7 @@ class ARQS(HipFlow):
             return
         state, _ = self._generic_forward_state(self._map(x, bounds, 0), direction, None,
                                                log_det if accumulate else log_det.zero_())
-        _lib.check(_lib.lib().nfx_arqs_bounds(_lib.ptr(state), _lib.ptr(bounds), _lib.ptr(out), x.shape[0], self.dim,
-                                              1, _lib.stream_of(x)), "nfx_arqs_bounds")
+        _lib.checked().nfx_arqs_bounds(state, bounds, out, x.shape[0], self.dim, 1, _lib.stream_of(x))
 
     # -- train-mode BatchNorm in the MADE: the reference's d calls, each with batch statistics -----
     def _dispatch(self, x, direction):
@@ -204,12 +200,12 @@ class ARQS(HipFlow):
 
     def _build_pack(self, device):
         d, H, K = self.dim, self.conditioner.hidden_dim, self.num_bins
-        L = _lib.lib()
+        L = _lib.checked()
         packed = torch.empty(L.nfx_arqs_packed_floats(d, H, K), device=device, dtype=torch.float32)
         lins = self.conditioner.linears()
         bns = self.conditioner.batchnorms() or ()
         raw, keep = _lib.mlp_raw(lins, bns, masks=[lin.mask for lin in lins])
-        _lib.check(L.nfx_arqs_pack(raw, d, H, K, _lib.ptr(packed), _lib.stream_of(packed)), "nfx_arqs_pack")
+        L.nfx_arqs_pack(raw, d, H, K, packed, _lib.stream_of(packed))
         packed._nfx_keep = keep
         return packed
 
@@ -277,11 +273,10 @@ class ARQS(HipFlow):
             return self._generic_launch(x, out, log_det, direction, accumulate)
         packed = self._packed(x.device, self._build_pack)
         rescale, lo, hi = self._rescale_scalars()
-        _lib.check(_lib.lib().nfx_arqs(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), x.shape[0], self.dim,
-            self.conditioner.hidden_dim, self.num_bins, float(self.min_bin_width),
-            float(self.min_bin_height), float(self.min_derivative), rescale, lo, hi, int(direction),
-            int(bool(accumulate)), _lib.stream_of(x)), "nfx_arqs")
+        _lib.checked().nfx_arqs(
+            packed, x, out, log_det, x.shape[0], self.dim, self.conditioner.hidden_dim, self.num_bins,
+            float(self.min_bin_width), float(self.min_bin_height), float(self.min_derivative), rescale, lo, hi,
+            int(direction), int(bool(accumulate)), _lib.stream_of(x))
 
 
 class _ArqsTrainFunction(torch.autograd.Function):

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from .. import _lib
 from .. import distributed as _dist
 from . import generic as _generic
-from .flow import HipFlow, STATS
+from .flow import HipFlow, STATS, timed
 
 MAX_H = 256       # eval kernels (H > 128: nfx_made_big.hip)
 MAX_H_BWD = 128   # fused backward kernels; wider layers: the any-shape path (csrc/nfx_generic.hip)
@@ -216,24 +216,22 @@ class _MadeAffineFlow(HipFlow):
         on the partial vector, each normalising with its own batch statistics and updating the
         running statistics (so d updates per forward), one element step each; then the guards.
         Returns (y, ld, work, wld, bnps, counts)."""
-        L = _lib.lib()
+        L = _lib.checked()
         x = x.detach().contiguous()
         B, d = x.shape
         variant = self._variant(direction)
         st = _lib.stream_of(x)
-        p = _lib.ptr
         work = torch.zeros_like(x)
         wld = torch.zeros(B, device=x.device, dtype=torch.float32)
         bnps, counts = [], []
         for i in range(d):
             prm, bnp, cnt = self._generic_made_bn_train(work)
-            _lib.check(L.nfx_made_elem_step(p(x), p(prm), p(work), p(wld), B, d, i, variant, st), "nfx_made_elem_step")
+            L.nfx_made_elem_step(x, prm, work, wld, B, d, i, variant, st)
             bnps.append(bnp)
             counts.append(cnt)
         y = torch.empty_like(x)
         ld = torch.empty(B, device=x.device, dtype=torch.float32)
-        _lib.check(L.nfx_made_elem_finish(p(x), p(work), p(wld), p(y), p(ld), B, d, variant, 0, st),
-                   "nfx_made_elem_finish")
+        L.nfx_made_elem_finish(x, work, wld, y, ld, B, d, variant, 0, st)
         return y, ld, work, wld, bnps, counts
 
     def _generic_seq_train_backward(self, x, gy, gld, direction, work, wld, bnps, counts):
@@ -243,26 +241,22 @@ class _MadeAffineFlow(HipFlow):
         step adjoint gives (dmu_i, dalpha_i) and dL/dx_i, and the batch-statistics MADE backward
         adds the call's parameter gradients and its input VJP into lam (columns >= i get exact
         zeros through the masks)."""
-        L = _lib.lib()
+        L = _lib.checked()
         B, d = x.shape
         variant = self._variant(direction)
         st = _lib.stream_of(x)
-        p = _lib.ptr
         lam = torch.empty_like(x)
-        _lib.check(L.nfx_made_elem_seq_backward(p(x), None, p(work), None, p(gy), p(gld), p(lam), B, d, variant, 0, st),
-                   "nfx_made_elem_seq_backward")
+        L.nfx_made_elem_seq_backward(x, None, work, None, gy, gld, lam, B, d, variant, 0, st)
         gx = torch.empty_like(x)
         wi = torch.empty_like(x)
         lins = self.conditioner.linears()
         bns = self.conditioner.batchnorms()
         acc = None
         for i in range(d - 1, -1, -1):
-            _lib.check(L.nfx_made_elem_prefix(p(work), p(wi), B, d, i, st), "nfx_made_elem_prefix")
+            L.nfx_made_elem_prefix(work, wi, B, d, i, st)
             masks, bnp, acts, prm = self._generic_made_bn(wi, bnps[i])
             dprm = torch.empty_like(prm)
-            _lib.check(L.nfx_made_elem_seq_step_backward(p(x), p(prm), p(work), p(wld), p(lam), p(gy), p(gld),
-                                                         p(dprm), p(gx), B, d, i, variant, st),
-                       "nfx_made_elem_seq_step_backward")
+            L.nfx_made_elem_seq_step_backward(x, prm, work, wld, lam, gy, gld, dprm, gx, B, d, i, variant, st)
             grads = _generic.made_bn_backward(wi, lins, masks, bns, bnp, acts, dprm, lam if i > 0 else None, True,
                                               counts[i], _dist.allreduce_bn_sums)
             acc = grads if acc is None else [a + g if g is not None else a for a, g in zip(acc, grads)]
@@ -271,15 +265,12 @@ class _MadeAffineFlow(HipFlow):
     def _generic_train_forward(self, x, direction):
         """One train-mode MADE call on x (made_bn_train_call: batch moments, SyncBN merge, running
         update, normalisation), then the parallel element map. Returns (y, ld, bnp, counts)."""
-        L = _lib.lib()
         x = x.detach().contiguous()
         B, d = x.shape
-        p = _lib.ptr
         prm, bnp, counts = self._generic_made_bn_train(x)
         y = torch.empty_like(x)
         ld = torch.empty(B, device=x.device, dtype=torch.float32)
-        _lib.check(L.nfx_made_elem_forward(p(x), p(prm), p(y), p(ld), B, d, self._variant(direction), 0,
-                                           _lib.stream_of(x)), "nfx_made_elem_forward")
+        _lib.checked().nfx_made_elem_forward(x, prm, y, ld, B, d, self._variant(direction), 0, _lib.stream_of(x))
         return y, ld, bnp, counts
 
     def _generic_bn_backward(self, x, gz, gld, direction, bnp=None, counts=None):
@@ -290,39 +281,35 @@ class _MadeAffineFlow(HipFlow):
         masks, bnp, acts, prm = self._generic_made_bn(x, bnp)
         gprm = torch.empty_like(prm)
         gx = torch.empty_like(x)
-        _lib.check(_lib.lib().nfx_made_elem_backward(_lib.ptr(x), _lib.ptr(prm), _lib.ptr(gz), _lib.ptr(gld),
-                                                     _lib.ptr(gprm), _lib.ptr(gx), B, d, self._variant(direction),
-                                                     _lib.stream_of(x)), "nfx_made_elem_backward")
+        _lib.checked().nfx_made_elem_backward(x, prm, gz, gld, gprm, gx, B, d, self._variant(direction),
+                                              _lib.stream_of(x))
         grads = _generic.made_bn_backward(x, self.conditioner.linears(), masks, self.conditioner.batchnorms(), bnp,
                                           acts, gprm, gx, train, counts, _dist.allreduce_bn_sums)
         return gx, grads
 
     def _generic_launch(self, x, out, log_det, direction, accumulate):
         variant = self._variant(direction)
-        L = _lib.lib()
+        L = _lib.checked()
         B, d = x.shape
         st = _lib.stream_of(x)
         if variant in (_lib.NFX_MAF_INVERSE, _lib.NFX_IAF_FORWARD):
             _, (_, _, _, prm) = self._generic_made(x)
-            _lib.check(L.nfx_made_elem_forward(_lib.ptr(x), _lib.ptr(prm), _lib.ptr(out), _lib.ptr(log_det), B, d,
-                                               variant, int(bool(accumulate)), st), "nfx_made_elem_forward")
+            L.nfx_made_elem_forward(x, prm, out, log_det, B, d, variant, int(bool(accumulate)), st)
             return
         work, wld = self._generic_seq_work(x, variant)
-        _lib.check(L.nfx_made_elem_finish(_lib.ptr(x), _lib.ptr(work), _lib.ptr(wld), _lib.ptr(out), _lib.ptr(log_det),
-                                          B, d, variant, int(bool(accumulate)), st), "nfx_made_elem_finish")
+        L.nfx_made_elem_finish(x, work, wld, out, log_det, B, d, variant, int(bool(accumulate)), st)
 
     def _generic_seq_work(self, x, variant):
         """A sequential direction as the reference runs it: d MADE calls, one element step each
         (nfx_made_elem_step); returns the raw vector and log-det before the final guards."""
         B, d = x.shape
-        L = _lib.lib()
+        L = _lib.checked()
         st = _lib.stream_of(x)
         work = torch.zeros_like(x)
         wld = torch.zeros(B, device=x.device, dtype=torch.float32)
         for i in range(d):
             _, (_, _, _, prm) = self._generic_made(work)
-            _lib.check(L.nfx_made_elem_step(_lib.ptr(x), _lib.ptr(prm), _lib.ptr(work), _lib.ptr(wld), B, d, i,
-                                            variant, st), "nfx_made_elem_step")
+            L.nfx_made_elem_step(x, prm, work, wld, B, d, i, variant, st)
         return work, wld
 
     def _generic_seq_backward(self, x, gz, gld, variant):
@@ -332,9 +319,8 @@ class _MadeAffineFlow(HipFlow):
         triangular system, by d - 1 substitution passes (each one MADE input-VJP, 4 GEMMs);
         then the weight gradients for dparams(lam) and dL/dx."""
         B, d = x.shape
-        L = _lib.lib()
+        L = _lib.checked()
         st = _lib.stream_of(x)
-        p = _lib.ptr
         work, _ = self._generic_seq_work(x, variant)
         lins = self.conditioner.linears()
         bns = self.conditioner.batchnorms()
@@ -343,22 +329,18 @@ class _MadeAffineFlow(HipFlow):
         else:
             masks, (h1, h2, h3, prm) = self._generic_made(work)
         gw = torch.empty_like(x)
-        _lib.check(L.nfx_made_elem_seq_backward(p(x), p(prm), p(work), None, p(gz), p(gld), p(gw), B, d, variant, 0,
-                                                st), "nfx_made_elem_seq_backward")
+        L.nfx_made_elem_seq_backward(x, prm, work, None, gz, gld, gw, B, d, variant, 0, st)
         lam = gw
         dprm = torch.empty_like(prm)
         for _ in range(d - 1):
-            _lib.check(L.nfx_made_elem_seq_backward(p(x), p(prm), p(work), p(lam), p(gz), p(gld), p(dprm), B, d,
-                                                    variant, 1, st), "nfx_made_elem_seq_backward")
+            L.nfx_made_elem_seq_backward(x, prm, work, lam, gz, gld, dprm, B, d, variant, 1, st)
             if bns:
                 lam = _generic.made_bn_input_vjp(dprm, lins, masks, bns, bnp, acts, gw.clone())
             else:
                 lam = _generic.made_input_vjp(dprm, lins, masks, h1, h2, h3, gw.clone())
-        _lib.check(L.nfx_made_elem_seq_backward(p(x), p(prm), p(work), p(lam), p(gz), p(gld), p(dprm), B, d,
-                                                variant, 1, st), "nfx_made_elem_seq_backward")
+        L.nfx_made_elem_seq_backward(x, prm, work, lam, gz, gld, dprm, B, d, variant, 1, st)
         gx = torch.empty_like(x)
-        _lib.check(L.nfx_made_elem_seq_backward(p(x), p(prm), p(work), p(lam), p(gz), p(gld), p(gx), B, d,
-                                                variant, 2, st), "nfx_made_elem_seq_backward")
+        L.nfx_made_elem_seq_backward(x, prm, work, lam, gz, gld, gx, B, d, variant, 2, st)
         if bns:
             return gx, _generic.made_bn_backward(work, lins, masks, bns, bnp, acts, dprm, None)
         return gx, _generic.made_backward(work, lins, masks, h1, h2, h3, dprm, None)
@@ -376,15 +358,13 @@ class _MadeAffineFlow(HipFlow):
         masks, (h1, h2, h3, prm) = self._generic_made(x)
         gprm = torch.empty_like(prm)
         gx = torch.empty_like(x)
-        _lib.check(_lib.lib().nfx_made_elem_backward(_lib.ptr(x), _lib.ptr(prm), _lib.ptr(gz), _lib.ptr(gld),
-                                                     _lib.ptr(gprm), _lib.ptr(gx), B, d, variant, _lib.stream_of(x)),
-                   "nfx_made_elem_backward")
+        _lib.checked().nfx_made_elem_backward(x, prm, gz, gld, gprm, gx, B, d, variant, _lib.stream_of(x))
         grads = _generic.made_backward(x, self.conditioner.linears(), masks, h1, h2, h3, gprm, gx)
         return gx, grads
 
     def _build_pack(self, device):
         d, H = self.dim, self.conditioner.hidden_dim
-        L = _lib.lib()
+        L = _lib.checked()
         packed = torch.empty(L.nfx_made_packed_floats(d, H), device=device, dtype=torch.float32)
         lins = self.conditioner.linears()
         bns = self.conditioner.batchnorms() or ()
@@ -392,10 +372,8 @@ class _MadeAffineFlow(HipFlow):
         # the parallel image (+ degree tables, extents); the sequential directions' image and chunk
         # schedule are added on the first sequential launch of this pack (_seq_packed): a training
         # step re-packs every layer, and the parallel directions never read them
-        _lib.check(L.nfx_made_pack_parallel(raw, d, H, _lib.ptr(packed), _lib.stream_of(packed)),
-                   "nfx_made_pack_parallel")
-        _lib.check(L.nfx_made_pack_backward(raw, d, H, _lib.ptr(packed), _lib.stream_of(packed)),
-                   "nfx_made_pack_backward")
+        L.nfx_made_pack_parallel(raw, d, H, packed, _lib.stream_of(packed))
+        L.nfx_made_pack_backward(raw, d, H, packed, _lib.stream_of(packed))
         packed._nfx_keep = keep
         packed._nfx_seq = False
         return packed
@@ -404,8 +382,8 @@ class _MadeAffineFlow(HipFlow):
         """`packed` with the sequential part built (nfx_made_pack_sequential) when `variant` is a
         sequential direction."""
         if variant in (_lib.NFX_MAF_FORWARD, _lib.NFX_IAF_INVERSE) and not getattr(packed, "_nfx_seq", True):
-            _lib.check(_lib.lib().nfx_made_pack_sequential(self.dim, self.conditioner.hidden_dim, _lib.ptr(packed),
-                                                           _lib.stream_of(packed)), "nfx_made_pack_sequential")
+            _lib.checked().nfx_made_pack_sequential(self.dim, self.conditioner.hidden_dim, packed,
+                                                    _lib.stream_of(packed))
             # under graph capture the build is only recorded: an eager call before the first
             # replay must build it again
             if not torch.cuda.is_current_stream_capturing():
@@ -453,43 +431,28 @@ class _MadeAffineFlow(HipFlow):
         B, d = x.shape
         H = self.conditioner.hidden_dim
         packed = self._packed(x.device, self._build_pack)
-        L = _lib.lib()
+        L = _lib.checked()
         gx = torch.empty_like(x)
         fac = torch.empty(L.nfx_made_backward_factor_floats(B, d, H), device=x.device, dtype=torch.float32)
         variant = self._variant(direction)
         parallel = variant in (_lib.NFX_MAF_INVERSE, _lib.NFX_IAF_FORWARD)
-        ev = BACKWARD_EVENTS
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
         fn = L.nfx_made_affine_backward if parallel else L.nfx_made_seq_backward
-        _lib.check(fn(_lib.ptr(packed), _lib.ptr(x), _lib.ptr(gz), _lib.ptr(gld), _lib.ptr(gx), _lib.ptr(fac),
-                      B, d, H, variant, _lib.stream_of(x)),
-                   "nfx_made_affine_backward" if parallel else "nfx_made_seq_backward")
-        if ev is not None:
-            e1.record()
-            ev.append(("made_bwd_kernel" if parallel else "made_seq_bwd_kernel", e0, e1))
+        with timed(BACKWARD_EVENTS, "made_bwd_kernel" if parallel else "made_seq_bwd_kernel"):
+            fn(packed, x, gz, gld, gx, fac, B, d, H, variant, _lib.stream_of(x))
         return gx, self._weight_grads(fac, B)
 
     def _weight_grads(self, fac, B):
         """MADE parameter gradients (parameters() order) from the feature-major factors:
         nfx_made_backward_weights (MFMA sample contractions, masks applied)."""
         d, H = self.dim, self.conditioner.hidden_dim
-        L = _lib.lib()
+        L = _lib.checked()
         dev = fac.device
         grads = torch.empty(L.nfx_made_param_floats(d, H), device=dev, dtype=torch.float32)
         ws = torch.empty(max(1, L.nfx_made_wgrad_workspace_bytes(B, d, H)), device=dev, dtype=torch.uint8)
         masks = [lin.mask.to(device=dev, dtype=torch.float32).contiguous() for lin in self.conditioner.linears()]
-        mp = (ctypes.c_void_p * 4)(*[_lib.ptr(m) for m in masks])
-        ev = BACKWARD_EVENTS
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(L.nfx_made_backward_weights(_lib.ptr(fac), B, d, H, mp, _lib.ptr(grads), _lib.ptr(ws),
-                                               _lib.stream_of(fac)), "nfx_made_backward_weights")
-        if ev is not None:
-            e1.record()
-            ev.append(("made_wgrad_kernel", e0, e1))
+        mp = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in masks])
+        with timed(BACKWARD_EVENTS, "made_wgrad_kernel"):
+            L.nfx_made_backward_weights(fac, B, d, H, mp, grads, ws, _lib.stream_of(fac))
         grads._nfx_keep = (masks, ws)
         out, o = [], 0
         for p in self.conditioner.parameters():
@@ -503,16 +466,16 @@ class _MadeAffineFlow(HipFlow):
             return self._generic_launch(x, out, log_det, direction, accumulate)
         variant = self._variant(direction)
         packed = self._seq_packed(self._packed(x.device, self._build_pack), variant)
-        _lib.check(_lib.lib().nfx_made_affine(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), x.shape[0], self.dim,
-            self.conditioner.hidden_dim, variant, int(bool(accumulate)),
-            _lib.stream_of(x)), "nfx_made_affine")
+        _lib.checked().nfx_made_affine(packed, x, out, log_det, x.shape[0], self.dim, self.conditioner.hidden_dim,
+                                       variant, int(bool(accumulate)), _lib.stream_of(x))
 
     def _hip_launch_logprob(self, x, out, log_det, logp, sums, workspace, accumulate):
         if not self._fused_family():
             return False
         variant = self._variant(-1)
         packed = self._seq_packed(self._packed(x.device, self._build_pack), variant)
+        # the one launch on the raw handle: NFX_EUNSUPPORTED is an answer here ("no fused kernel,
+        # run the plain inverse"), which the checked handle would raise as an error
         rc = _lib.lib().nfx_made_affine_logprob(
             _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), _lib.ptr(logp),
             _lib.ptr(sums), _lib.ptr(workspace), x.shape[0], self.dim,
@@ -525,30 +488,15 @@ class _MadeAffineFlow(HipFlow):
 
 def made_bn_train_call(conditioner, masks, h):
     """One train-mode call of a BatchNorm MADE (use_batch_norm=True, made.py:93-106) on h: per
-    BatchNorm the batch moments (nfx_flowbn_moments, SyncBN-merged), the running update and the
-    normalisation (nfx_bn_prepare), ReLU; returns (params, bnp, counts), bnp / counts being what the
+    BatchNorm the batch moments (SyncBN-merged), the running update and the normalisation
+    (generic.bn_train_prepare), ReLU; returns (params, bnp, counts), bnp / counts being what the
     batch-statistics backward (generic.made_bn_backward(train=True)) needs."""
-    L = _lib.lib()
-    B = h.shape[0]
-    dev = h.device
-    st = _lib.stream_of(h)
-    p = _lib.ptr
     lins = conditioner.linears()
     bns = conditioner.batchnorms()
     bnp, counts = [], []
     for i, bn in enumerate(bns):
         z = _generic.linear_forward(h, lins[i], wmask=masks[i])
-        H = z.shape[1]
-        ws = torch.empty(max(1, L.nfx_flowbn_workspace_bytes(B, H)), device=dev, dtype=torch.uint8)
-        stats = torch.empty(H, 3, device=dev, dtype=torch.float64)
-        _lib.check(L.nfx_flowbn_moments(p(z), B, H, p(stats), p(ws), st), "nfx_flowbn_moments")
-        _dist.merge_bn_stats(stats)
-        t = torch.empty(4, H, device=dev, dtype=torch.float32)
-        _lib.check(L.nfx_bn_prepare(p(stats), p(bn.weight.detach()), p(bn.bias.detach()), p(bn.running_mean),
-                                    p(bn.running_var), float(bn.eps), float(bn.momentum), 1, H, p(t[0]), p(t[1]),
-                                    p(t[2]), p(t[3]), st), "nfx_bn_prepare")
-        torch.autograd.graph.increment_version(bn.running_mean)
-        torch.autograd.graph.increment_version(bn.running_var)
+        t, stats = _generic.bn_train_prepare(z, bn, _dist.merge_bn_stats)
         h = _generic.bn_apply_relu(z, t)
         bnp.append(t)
         counts.append(stats)  # stats[0, 0] = the global sample count
@@ -558,17 +506,7 @@ def made_bn_train_call(conditioner, masks, h):
 
 def made_bn_eval_params(conditioner, device):
     """Per MADE BatchNorm [mean, invstd, scale, shift] from the running statistics (eval mode)."""
-    L = _lib.lib()
-    out = []
-    for bn in conditioner.batchnorms():
-        H = bn.num_features
-        t = torch.empty(4, H, device=device, dtype=torch.float32)
-        _lib.check(L.nfx_bn_prepare(None, _lib.ptr(bn.weight.detach()), _lib.ptr(bn.bias.detach()),
-                                    _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps), 0.0, 0,
-                                    H, _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(t[2]), _lib.ptr(t[3]),
-                                    _lib.stream_of(t)), "nfx_bn_prepare")
-        out.append(t)
-    return out
+    return _generic.bn_eval_params(conditioner.batchnorms(), device)
 
 
 def bn_train_supported(conditioner, x, dim):

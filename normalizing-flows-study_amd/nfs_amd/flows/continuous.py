@@ -174,19 +174,17 @@ class ContinuousFlow(HipFlow):
         return True, ""
 
     def _build_pack(self, device):
-        L = _lib.lib()
+        L = _lib.checked()
         d, H = self.dim, self.hidden_dim
         packed = torch.empty(L.nfx_cnf_packed_floats(d, H), device=device, dtype=torch.float32)
         t = [p.detach().to(device=device, dtype=torch.float32).contiguous()
              for lin in self.ode_func.linears() for p in (lin.weight, lin.bias)]
-        _lib.check(L.nfx_cnf_pack(*[_lib.ptr(p) for p in t], d, H, _lib.ptr(packed), _lib.stream_of(packed)),
-                   "nfx_cnf_pack")
+        L.nfx_cnf_pack(*t, d, H, packed, _lib.stream_of(packed))
         return packed
 
     def _hip_launch(self, x, out, log_det, direction, accumulate):
         packed = self._packed(x.device, self._build_pack)
         times = self._times(direction).float()
-        _lib.check(_lib.lib().nfx_cnf_integrate(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), x.shape[0], self.dim,
-            self.hidden_dim, float(times[0]), float(times[1]), float(torch.tensor(self.step_size)),
-            int(bool(accumulate)), _lib.stream_of(x)), "nfx_cnf_integrate")
+        _lib.checked().nfx_cnf_integrate(
+            packed, x, out, log_det, x.shape[0], self.dim, self.hidden_dim, float(times[0]), float(times[1]),
+            float(torch.tensor(self.step_size)), int(bool(accumulate)), _lib.stream_of(x))

@@ -29,7 +29,7 @@ import torch.nn as nn
 from .. import _lib
 from .. import distributed as _dist
 from . import generic as _generic
-from .flow import HipFlow, STATS
+from .flow import HipFlow, STATS, timed
 
 MAX_D = 64          # eval kernels: affine_coupling_kernel (d <= 8) / affine_wide_kernel (d <= 64)
 MAX_D_TRAIN = 8     # train-mode / backward kernels
@@ -81,18 +81,16 @@ def chain_ok(flows, x):
 def chain_launch(flows, x, out, ld, direction, accumulate, logprob=None):
     """All `flows` (in module order) in one nfx_affine_chain launch; with logprob=(logp, sums,
     workspace) an inverse chain also writes the Gaussian log-density and NLL partials."""
-    packs = (ctypes_vp * len(flows))(*[_lib.ptr(f._packed(x.device, f._build_pack)) for f in flows])
-    L = _lib.lib()
+    packs = (ctypes_vp * len(flows))(*[f._packed(x.device, f._build_pack).data_ptr() for f in flows])
+    L = _lib.checked()
     d, H = flows[0].data_dim, flows[0]._hidden()
-    p = _lib.ptr
     if logprob is not None:
         logp, sums, ws = logprob
-        _lib.check(L.nfx_affine_chain_logprob(packs, len(flows), p(x), p(out), p(ld), p(logp), p(sums), p(ws),
-                                              x.shape[0], d, H, int(bool(accumulate)), _lib.stream_of(x)),
-                   "nfx_affine_chain_logprob")
+        L.nfx_affine_chain_logprob(packs, len(flows), x, out, ld, logp, sums, ws, x.shape[0], d, H,
+                                   int(bool(accumulate)), _lib.stream_of(x))
     else:
-        _lib.check(L.nfx_affine_chain(packs, len(flows), p(x), p(out), p(ld), x.shape[0], d, H, int(direction),
-                                      int(bool(accumulate)), _lib.stream_of(x)), "nfx_affine_chain")
+        L.nfx_affine_chain(packs, len(flows), x, out, ld, x.shape[0], d, H, int(direction), int(bool(accumulate)),
+                           _lib.stream_of(x))
     STATS["hip"] += 1
 
 
@@ -119,12 +117,10 @@ SAMPLE_CHAIN_MAX_B = 1 << 16
 def chain_sample(flows, rng_state, seed, z, x, ld):
     """z ~ N(0, I) drawn on the device and x, ld = forward(z) through every flow, one launch
     (nfx_affine_chain_sample); rng_state = the device uint64[2] generator state it advances."""
-    packs = (ctypes_vp * len(flows))(*[_lib.ptr(f._packed(x.device, f._build_pack)) for f in flows])
+    packs = (ctypes_vp * len(flows))(*[f._packed(x.device, f._build_pack).data_ptr() for f in flows])
     d, H = flows[0].data_dim, flows[0]._hidden()
-    p = _lib.ptr
-    _lib.check(_lib.lib().nfx_affine_chain_sample(packs, len(flows), int(seed) & ((1 << 64) - 1), p(rng_state), p(z),
-                                                  p(x), p(ld), x.shape[0], d, H, _lib.stream_of(x)),
-               "nfx_affine_chain_sample")
+    _lib.checked().nfx_affine_chain_sample(packs, len(flows), int(seed) & ((1 << 64) - 1), rng_state, z, x, ld,
+                                           x.shape[0], d, H, _lib.stream_of(x))
     STATS["hip"] += 1
 
 
@@ -274,18 +270,7 @@ class CouplingLayer(HipFlow):
     def _generic_bn_eval(self, device):
         """Per conditioner BatchNorm [4][H] = (mean, invstd, scale, shift) from the running
         statistics (nfx_bn_prepare), cached with the parameters."""
-        L = _lib.lib()
-        H = self._hidden()
-        out = []
-        for _, bn1, _, bn2, _ in self._generic_nets():
-            for bn in (bn1, bn2):
-                t = torch.empty(4, H, device=device, dtype=torch.float32)
-                _lib.check(L.nfx_bn_prepare(None, _lib.ptr(bn.weight.detach()), _lib.ptr(bn.bias.detach()),
-                                            _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var), float(bn.eps), 0.0,
-                                            0, H, _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(t[2]), _lib.ptr(t[3]),
-                                            _lib.stream_of(t)), "nfx_bn_prepare")
-                out.append(t)
-        return out
+        return _generic.bn_eval_params([self.s_net[1], self.s_net[4], self.b_net[1], self.b_net[4]], device)
 
     def _mask_dev(self, device):
         return self.mask.detach().to(device=device, dtype=torch.float32).contiguous()
@@ -299,26 +284,18 @@ class CouplingLayer(HipFlow):
             h1 = _generic.linear_forward(x, l1, in_scale=mask, relu=True, post=(p1[2], p1[3]))
             h2 = _generic.linear_forward(h1, l2, relu=True, post=(p2[2], p2[3]))
             raw.append(_generic.linear_forward(h2, l3))
-        _lib.check(_lib.lib().nfx_affine_elem_forward(
-            _lib.ptr(x), _lib.ptr(raw[0]), _lib.ptr(raw[1]), _lib.ptr(mask), _lib.ptr(out), _lib.ptr(log_det),
-            x.shape[0], self.data_dim, int(direction), int(bool(accumulate)), _lib.stream_of(x)),
-            "nfx_affine_elem_forward")
+        _lib.checked().nfx_affine_elem_forward(x, raw[0], raw[1], mask, out, log_det, x.shape[0], self.data_dim,
+                                               int(direction), int(bool(accumulate)), _lib.stream_of(x))
 
     def _generic_acts(self, x, mask, bnp):
         """Conditioner recompute with given BatchNorm (mean, invstd, scale, shift): per net
         (z1, h1, z2, h2, raw output)."""
-        L = _lib.lib()
-        B, H = x.shape[0], self._hidden()
         acts = []
         for i, (l1, _, l2, _, l3) in enumerate(self._generic_nets()):
             z1 = _generic.linear_forward(x, l1, in_scale=mask)
-            h1 = torch.empty_like(z1)
-            _lib.check(L.nfx_bn_apply_relu(_lib.ptr(z1), _lib.ptr(bnp[2 * i][2]), _lib.ptr(bnp[2 * i][3]),
-                                           _lib.ptr(h1), B, H, _lib.stream_of(x)), "nfx_bn_apply_relu")
+            h1 = _generic.bn_apply_relu(z1, bnp[2 * i])
             z2 = _generic.linear_forward(h1, l2)
-            h2 = torch.empty_like(z2)
-            _lib.check(L.nfx_bn_apply_relu(_lib.ptr(z2), _lib.ptr(bnp[2 * i + 1][2]), _lib.ptr(bnp[2 * i + 1][3]),
-                                           _lib.ptr(h2), B, H, _lib.stream_of(x)), "nfx_bn_apply_relu")
+            h2 = _generic.bn_apply_relu(z2, bnp[2 * i + 1])
             acts.append((z1, h1, z2, h2, _generic.linear_forward(h2, l3)))
         return acts
 
@@ -326,40 +303,25 @@ class CouplingLayer(HipFlow):
         """Train mode on the any-shape path: per conditioner BatchNorm the batch moments
         (nfx_flowbn_moments, SyncBN-merged), mean/invstd/scale/shift and the running update
         (nfx_bn_prepare), then the affine element map. Returns (y, ld, bnp, counts)."""
-        L = _lib.lib()
         x = x.detach().contiguous()
         B, d = x.shape
-        H = self._hidden()
-        dev = x.device
-        st = _lib.stream_of(x)
-        p = _lib.ptr
-        mask = self._mask_dev(dev)
-        ws = torch.empty(max(1, L.nfx_flowbn_workspace_bytes(B, H)), device=dev, dtype=torch.uint8)
+        mask = self._mask_dev(x.device)
         bnp, counts, raw = [], [], []
         for l1, bn1, l2, bn2, l3 in self._generic_nets():
             h = x
             for lin, bn, first in ((l1, bn1, True), (l2, bn2, False)):
                 z = _generic.linear_forward(h, lin, in_scale=mask if first else None)
-                stats = torch.empty(H, 3, device=dev, dtype=torch.float64)
-                _lib.check(L.nfx_flowbn_moments(p(z), B, H, p(stats), p(ws), st), "nfx_flowbn_moments")
-                _dist.merge_bn_stats(stats)
-                t = torch.empty(4, H, device=dev, dtype=torch.float32)
-                _lib.check(L.nfx_bn_prepare(p(stats), p(bn.weight.detach()), p(bn.bias.detach()), p(bn.running_mean),
-                                            p(bn.running_var), float(bn.eps), float(bn.momentum), 1, H, p(t[0]),
-                                            p(t[1]), p(t[2]), p(t[3]), st), "nfx_bn_prepare")
-                torch.autograd.graph.increment_version(bn.running_mean)
-                torch.autograd.graph.increment_version(bn.running_var)
-                h = torch.empty_like(z)
-                _lib.check(L.nfx_bn_apply_relu(p(z), p(t[2]), p(t[3]), p(h), B, H, st), "nfx_bn_apply_relu")
+                t, stats = _generic.bn_train_prepare(z, bn, _dist.merge_bn_stats)
+                h = _generic.bn_apply_relu(z, t)
                 bnp.append(t)
                 counts.append(stats)  # stats[0, 0] = the global sample count
             raw.append(_generic.linear_forward(h, l3))
         bns = [self.s_net[1], self.s_net[4], self.b_net[1], self.b_net[4]]
         torch._foreach_add_([bn.num_batches_tracked for bn in bns], 1)
         y = torch.empty_like(x)
-        ld = torch.empty(B, device=dev, dtype=torch.float32)
-        _lib.check(L.nfx_affine_elem_forward(p(x), p(raw[0]), p(raw[1]), p(mask), p(y), p(ld), B, d, int(direction), 0,
-                                             st), "nfx_affine_elem_forward")
+        ld = torch.empty(B, device=x.device, dtype=torch.float32)
+        _lib.checked().nfx_affine_elem_forward(x, raw[0], raw[1], mask, y, ld, B, d, int(direction), 0,
+                                               _lib.stream_of(x))
         return y, ld, bnp, counts
 
     def _generic_backward(self, x, gy, gld, direction, bnp, counts):
@@ -367,17 +329,12 @@ class CouplingLayer(HipFlow):
         conditioner recomputed with the call's BatchNorm normalisation, the affine element adjoint,
         then per net the Linear / BatchNorm / ReLU backward (train: batch-statistics BatchNorm
         backward with SyncBN-summed float64 sums; counts = None: eval, running statistics)."""
-        L = _lib.lib()
         B, d = x.shape
-        H = self._hidden()
-        st = _lib.stream_of(x)
-        p = _lib.ptr
         mask = self._mask_dev(x.device)
         acts = self._generic_acts(x, mask, bnp)
         gs, gb, gx = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-        _lib.check(L.nfx_affine_elem_backward(p(x), p(acts[0][4]), p(acts[1][4]), p(mask), p(gy), p(gld), p(gs), p(gb),
-                                              p(gx), B, d, int(direction), st), "nfx_affine_elem_backward")
-        ws = torch.empty(max(1, L.nfx_bn_workspace_bytes(B, H)), device=x.device, dtype=torch.uint8)
+        _lib.checked().nfx_affine_elem_backward(x, acts[0][4], acts[1][4], mask, gy, gld, gs, gb, gx, B, d,
+                                                int(direction), _lib.stream_of(x))
         train = counts is not None
         grads = []
         for i, ((l1, bn1, l2, bn2, l3), g_out) in enumerate(zip(self._generic_nets(), (gs, gb))):
@@ -386,17 +343,9 @@ class CouplingLayer(HipFlow):
             g = _generic.linear_backward_data(g_out, l3, act=h2)
             per = []
             for z, hin, lin, bn, k in ((z2, h1, l2, bn2, 2 * i + 1), (z1, x, l1, bn1, 2 * i)):
-                t = bnp[k]
-                sums = torch.empty(2, H, device=x.device, dtype=torch.float64)
-                _lib.check(L.nfx_bn_backward_sums(p(g), p(z), p(t[0]), p(t[1]), p(sums), B, H, p(ws), st),
-                           "nfx_bn_backward_sums")
-                if train:
-                    _dist.allreduce_bn_sums(sums)
-                gz = torch.empty_like(g)
                 # train: the global sample count = n of the merged moments triple (device float64)
-                _lib.check(L.nfx_bn_backward_apply(p(g), p(z), p(t[0]), p(t[1]), p(bn.weight.detach()), p(sums),
-                                                   p(counts[k]) if train else None, int(train), p(gz), B, H, st),
-                           "nfx_bn_backward_apply")
+                gz, sums = _generic.bn_backward(g, z, bnp[k], bn.weight.detach(), train, counts[k] if train else None,
+                                                _dist.allreduce_bn_sums)
                 first = lin is l1
                 wl = _generic.linear_backward_weight(gz, hin, lin, in_scale=mask if first else None)
                 if first:
@@ -430,14 +379,14 @@ class CouplingLayer(HipFlow):
         backward's first two passes, which then skip recomputing layers 1-2."""
         if not self._fused_train():
             return self._generic_train_forward(x, direction)
-        L = _lib.lib()
+        L = _lib.checked()
         x = x.detach().contiguous()
         B, d = x.shape
         H = self._hidden()
         dev = x.device
         st = _lib.stream_of(x)
         s_raw, b_raw, keep_src = self._raw_nets()
-        mask = self.mask.detach().to(device=dev, dtype=torch.float32).contiguous()
+        mask = self._mask_dev(dev)
         nst = L.nfx_affine_train_stats_doubles(H)
         stats = torch.empty(2, nst, device=dev, dtype=torch.float64)
         tpack = torch.empty(L.nfx_affine_train_pack_floats(d, H), device=dev, dtype=torch.float32)
@@ -454,50 +403,30 @@ class CouplingLayer(HipFlow):
             weakref.finalize(h2, _keep_release, rel, 4 * nkeep)
         KEEP_STATS["kept" if h2 is not None else "recompute"] += 1
         ev = TRAIN_EVENTS
-        p = _lib.ptr
-        _lib.check(L.nfx_affine_train_pack(s_raw, b_raw, p(mask), None, None, d, H, p(tpack), None, st),
-                   "nfx_affine_train_pack")
+        kn = "affine_trainw_kernel" if H > 64 else "affine_train_kernel"
+        L.nfx_affine_train_pack(s_raw, b_raw, mask, None, None, d, H, tpack, None, st)
         for layer in (1, 2):
-            if ev is not None:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-            _lib.check(L.nfx_affine_train_stats_keep(p(tpack), p(x), B, d, H, layer, p(stats[layer - 1]), p(ws),
-                                                     p(h2) if (h2 is not None and layer == 2) else None, st),
-                       "nfx_affine_train_stats")
-            if ev is not None:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record()
-                kn = "affine_trainw_kernel" if H > 64 else "affine_train_kernel"
-                ev.append((f"{kn}<STATS{layer}>", e0, e1))
+            with timed(ev, f"{kn}<STATS{layer}>"):
+                L.nfx_affine_train_stats_keep(tpack, x, B, d, H, layer, stats[layer - 1], ws,
+                                              h2 if layer == 2 else None, st)
             _dist.merge_bn_stats(stats[layer - 1].view(2, -1, 3))
-            _lib.check(L.nfx_affine_train_pack(s_raw, b_raw, p(mask), p(stats[0]),
-                                               p(stats[1]) if layer == 2 else None, d, H, p(tpack),
-                                               p(epack) if (layer == 2 and h2 is None) else None, st),
-                       "nfx_affine_train_pack")  # (kept pre-activations: OUTK needs no eval image)
+            # (kept pre-activations: OUTK needs no eval image)
+            L.nfx_affine_train_pack(s_raw, b_raw, mask, stats[0], stats[1] if layer == 2 else None, d, H, tpack,
+                                    epack if (layer == 2 and h2 is None) else None, st)
         y = torch.empty_like(x)
         ld = torch.empty(B, device=dev, dtype=torch.float32)
-        if ev is not None:
-            e0 = torch.cuda.Event(enable_timing=True)
-            e0.record()
-        if h2 is not None:  # from the kept pre-activations (no layer 1-2 recompute)
-            _lib.check(L.nfx_affine_train_output(p(tpack), p(x), p(h2), p(y), p(ld), B, d, H, int(direction), st),
-                       "nfx_affine_train_output")
-        else:
-            _lib.check(L.nfx_affine_coupling(p(epack), p(x), p(y), p(ld), B, d, H, int(direction), 0, st),
-                       "nfx_affine_coupling")
-        if ev is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            ev.append(("affine_train_kernel<OUTK>" if h2 is not None else "affine_coupling_kernel", e0, e1))
+        with timed(ev, "affine_train_kernel<OUTK>" if h2 is not None else "affine_coupling_kernel"):
+            if h2 is not None:  # from the kept pre-activations (no layer 1-2 recompute)
+                L.nfx_affine_train_output(tpack, x, h2, y, ld, B, d, H, int(direction), st)
+            else:
+                L.nfx_affine_coupling(epack, x, y, ld, B, d, H, int(direction), 0, st)
         bns = [self.s_net[1], self.s_net[4], self.b_net[1], self.b_net[4]]
         rm = (ctypes_vp * 4)(*[bn.running_mean.data_ptr() for bn in bns])
         rv = (ctypes_vp * 4)(*[bn.running_var.data_ptr() for bn in bns])
         counted = all(bn.num_batches_tracked is not None and bn.num_batches_tracked.dtype == torch.int64
                       and bn.num_batches_tracked.device == dev for bn in bns)
         nb = (ctypes_vp * 4)(*[bn.num_batches_tracked.data_ptr() for bn in bns]) if counted else None
-        _lib.check(L.nfx_affine_train_update_running_counted(p(stats[0]), p(stats[1]), rm, rv, nb, H,
-                                                             float(bns[0].momentum), st),
-                   "nfx_affine_train_update_running")
+        L.nfx_affine_train_update_running_counted(stats[0], stats[1], rm, rv, nb, H, float(bns[0].momentum), st)
         for bn in bns:
             torch.autograd.graph.increment_version(bn.running_mean)
             torch.autograd.graph.increment_version(bn.running_var)
@@ -521,20 +450,18 @@ class CouplingLayer(HipFlow):
         return x.shape[1] == self.data_dim  # fused (d <= 8, H <= 128) or the any-shape path
 
     def _build_eval_backward_pack(self, device):
-        L = _lib.lib()
+        L = _lib.checked()
         d, H = self.data_dim, self._hidden()
         s_raw, b_raw, keep = self._raw_nets()
-        mask = self.mask.detach().to(device=device, dtype=torch.float32).contiguous()
+        mask = self._mask_dev(device)
         stats = torch.empty(2, L.nfx_affine_train_stats_doubles(H), device=device, dtype=torch.float64)
         st = _lib.stream_of(stats)
         bns = [self.s_net[1], self.s_net[4], self.b_net[1], self.b_net[4]]
         rm = (ctypes_vp * 4)(*[bn.running_mean.data_ptr() for bn in bns])
         rv = (ctypes_vp * 4)(*[bn.running_var.data_ptr() for bn in bns])
-        p = _lib.ptr
-        _lib.check(L.nfx_affine_eval_stats(rm, rv, H, p(stats[0]), p(stats[1]), st), "nfx_affine_eval_stats")
+        L.nfx_affine_eval_stats(rm, rv, H, stats[0], stats[1], st)
         tpack = torch.empty(L.nfx_affine_train_pack_floats(d, H), device=device, dtype=torch.float32)
-        _lib.check(L.nfx_affine_train_pack(s_raw, b_raw, p(mask), p(stats[0]), p(stats[1]), d, H, p(tpack), None, st),
-                   "nfx_affine_train_pack")
+        L.nfx_affine_train_pack(s_raw, b_raw, mask, stats[0], stats[1], d, H, tpack, None, st)
         tpack._nfx_keep = (keep, mask)
         return tpack, stats
 
@@ -551,7 +478,7 @@ class CouplingLayer(HipFlow):
     def _train_backward(self, x, gy, gld, direction, tpack, stats, sync=True, h2=None):
         """dL/dx and the parameter gradients (parameters() order) of one train-mode call
         (sync=False: eval mode, the BatchNorm sums are plain parameter-gradient partials)."""
-        L = _lib.lib()
+        L = _lib.checked()
         x = x.contiguous()
         B, d = x.shape
         H = self._hidden()
@@ -568,27 +495,16 @@ class CouplingLayer(HipFlow):
         s_blocks = {1: G[0:4 * Hp], 2: G[4 * Hp + 2 * (D * Hp + D):][:4 * Hp]}
         if h2 is None:  # kept by a train-mode forward (else: recompute)
             h2 = getattr(tpack, "_nfx_h2", None)
-        p = _lib.ptr
         ev = TRAIN_EVENTS
+        kn = "affine_trainw_kernel" if H > 64 else "affine_train_kernel"
         for stage in (1, 2, 3):
-            if ev is not None:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-            kept = h2 if stage < 3 else None
-            _lib.check(L.nfx_affine_train_backward_keep(p(tpack), p(x), p(gy), p(gld), p(gx), B, d, H,
-                                                        int(direction), stage, p(stats[1]), p(G), p(ws),
-                                                        p(kept) if kept is not None else None, st),
-                       "nfx_affine_train_backward")
-            if ev is not None:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record()
-                kn = "affine_trainw_kernel" if H > 64 else "affine_train_kernel"
-                ev.append((f"{kn}<BWD{stage}>", e0, e1))
+            with timed(ev, f"{kn}<BWD{stage}>"):
+                L.nfx_affine_train_backward_keep(tpack, x, gy, gld, gx, B, d, H, int(direction), stage, stats[1], G,
+                                                 ws, h2 if stage < 3 else None, st)
             if sync and stage in s_blocks:
                 _dist.allreduce_bn_sums(s_blocks[stage])
         grads = torch.empty(L.nfx_affine_train_param_floats(d, H), device=dev, dtype=torch.float32)
-        _lib.check(L.nfx_affine_train_assemble(p(G), p(stats[0]), p(stats[1]), d, H, float(self.s_net[1].eps),
-                                               p(grads), st), "nfx_affine_train_assemble")
+        L.nfx_affine_train_assemble(G, stats[0], stats[1], d, H, float(self.s_net[1].eps), grads, st)
         out, o = [], 0
         for prm in self.parameters():
             n = prm.numel()
@@ -605,34 +521,26 @@ class CouplingLayer(HipFlow):
 
     def _build_pack(self, device):
         d, H = self.data_dim, self._hidden()
-        L = _lib.lib()
-        n = L.nfx_affine_packed_floats(d, H)
-        packed = torch.empty(n, device=device, dtype=torch.float32)
-        s_raw, k1 = _lib.mlp_raw([self.s_net[0], self.s_net[3], self.s_net[6]],
-                                 [self.s_net[1], self.s_net[4]])
-        b_raw, k2 = _lib.mlp_raw([self.b_net[0], self.b_net[3], self.b_net[6]],
-                                 [self.b_net[1], self.b_net[4]])
-        mask = self.mask.detach().to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(L.nfx_affine_pack(s_raw, b_raw, _lib.ptr(mask), d, H, _lib.ptr(packed),
-                                     _lib.stream_of(packed)), "nfx_affine_pack")
-        packed._nfx_keep = (k1, k2, mask)  # sources stay alive while the pack kernel is queued
+        L = _lib.checked()
+        packed = torch.empty(L.nfx_affine_packed_floats(d, H), device=device, dtype=torch.float32)
+        s_raw, b_raw, keep = self._raw_nets()
+        mask = self._mask_dev(device)
+        L.nfx_affine_pack(s_raw, b_raw, mask, d, H, packed, _lib.stream_of(packed))
+        packed._nfx_keep = (keep, mask)  # sources stay alive while the pack kernel is queued
         return packed
 
     def _hip_launch(self, x, out, log_det, direction, accumulate):
         if not self._fused_family():
             return self._generic_launch(x, out, log_det, direction, accumulate)
         packed = self._packed(x.device, self._build_pack)
-        _lib.check(_lib.lib().nfx_affine_coupling(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), x.shape[0],
-            self.data_dim, self._hidden(), int(direction), int(bool(accumulate)),
-            _lib.stream_of(x)), "nfx_affine_coupling")
+        _lib.checked().nfx_affine_coupling(packed, x, out, log_det, x.shape[0], self.data_dim, self._hidden(),
+                                           int(direction), int(bool(accumulate)), _lib.stream_of(x))
 
     def _hip_launch_logprob(self, x, out, log_det, logp, sums, workspace, accumulate):
         if not self._fused_family():
             return False
         packed = self._packed(x.device, self._build_pack)
-        _lib.check(_lib.lib().nfx_affine_coupling_logprob(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), _lib.ptr(logp),
-            _lib.ptr(sums), _lib.ptr(workspace), x.shape[0], self.data_dim, self._hidden(),
-            int(bool(accumulate)), _lib.stream_of(x)), "nfx_affine_coupling_logprob")
+        _lib.checked().nfx_affine_coupling_logprob(packed, x, out, log_det, logp, sums, workspace, x.shape[0],
+                                                   self.data_dim, self._hidden(), int(bool(accumulate)),
+                                                   _lib.stream_of(x))
         return True

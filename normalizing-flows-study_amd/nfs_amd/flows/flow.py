@@ -19,8 +19,6 @@ silently running eager (set nfs_amd.flows.flow.ALLOW_TORCH_FALLBACK = True to pe
 import torch
 import torch.nn as nn
 
-from .. import _lib
-
 ALLOW_TORCH_FALLBACK = False
 
 # Counters so tests and the bench can prove which path ran.
@@ -30,6 +28,27 @@ STATS = {"hip": 0, "torch": 0}
 def reset_stats():
     STATS["hip"] = 0
     STATS["torch"] = 0
+
+
+class timed:
+    """`with timed(events, name):` records a HIP event on the current stream before and after
+    the body and appends (name, start, end) to `events` (the TRAIN_EVENTS / BACKWARD_EVENTS lists
+    bench.py installs); with events = None it does nothing."""
+    __slots__ = ("events", "name", "start")
+
+    def __init__(self, events, name):
+        self.events, self.name = events, name
+
+    def __enter__(self):
+        if self.events is not None:
+            self.start = torch.cuda.Event(enable_timing=True)
+            self.start.record()
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.events is not None and exc_type is None:
+            end = torch.cuda.Event(enable_timing=True)
+            end.record()
+            self.events.append((self.name, self.start, end))
 
 
 class Flow(nn.Module):
@@ -286,7 +305,3 @@ class SequentialFlow(Flow):
             f._hip_launch_counted(cur, bufs[k], ld, direction, accumulate=True)
             cur, k = bufs[k], k ^ 1
         return cur, ld
-
-
-def stream_ptr(t):
-    return _lib.stream_of(t)

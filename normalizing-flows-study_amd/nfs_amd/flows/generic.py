@@ -19,9 +19,8 @@ def linear_forward(x, lin, in_scale=None, relu=False, wmask=None, post=None):
     w = lin.weight.detach()
     b = None if lin.bias is None else lin.bias.detach()
     ps, pt = (None, None) if post is None else post
-    _lib.check(_lib.lib().nfx_linear_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(wmask), _lib.ptr(b),
-                                             _lib.ptr(in_scale), _lib.ptr(ps), _lib.ptr(pt), _lib.ptr(y),
-                                             M, K, N, int(bool(relu)), _lib.stream_of(x)), "nfx_linear_forward")
+    _lib.checked().nfx_linear_forward(x, w, wmask, b, in_scale, ps, pt, y, M, K, N, int(bool(relu)),
+                                      _lib.stream_of(x))
     return y
 
 
@@ -33,9 +32,8 @@ def linear_backward_data(gy, lin, act=None, out_scale=None, out=None, wmask=None
     acc = out is not None
     if out is None:
         out = torch.empty(M, K, device=gy.device, dtype=torch.float32)
-    _lib.check(_lib.lib().nfx_linear_backward_data(_lib.ptr(gy), _lib.ptr(lin.weight.detach()), _lib.ptr(wmask),
-                                                   _lib.ptr(act), _lib.ptr(out_scale), _lib.ptr(out), M, N, K,
-                                                   int(acc), _lib.stream_of(gy)), "nfx_linear_backward_data")
+    _lib.checked().nfx_linear_backward_data(gy, lin.weight.detach(), wmask, act, out_scale, out, M, N, K, int(acc),
+                                            _lib.stream_of(gy))
     return out
 
 
@@ -44,13 +42,11 @@ def linear_backward_weight(gy, x, lin, in_scale=None, wmask=None):
     column sums of gy."""
     M, N = gy.shape
     K = lin.in_features
-    L = _lib.lib()
+    L = _lib.checked()
     gw = torch.empty(N, K, device=gy.device, dtype=torch.float32)
     gb = None if lin.bias is None else torch.empty(N, device=gy.device, dtype=torch.float32)
     ws = torch.empty(max(1, L.nfx_linear_workspace_bytes(M, N, K)), device=gy.device, dtype=torch.uint8)
-    _lib.check(L.nfx_linear_backward_weight(_lib.ptr(gy), _lib.ptr(x), _lib.ptr(in_scale), _lib.ptr(wmask),
-                                            _lib.ptr(gw), _lib.ptr(gb), M, N, K, _lib.ptr(ws), _lib.stream_of(gy)),
-               "nfx_linear_backward_weight")
+    L.nfx_linear_backward_weight(gy, x, in_scale, wmask, gw, gb, M, N, K, ws, _lib.stream_of(gy))
     return gw, gb
 
 
@@ -145,12 +141,45 @@ def made_backward_rows(x, lins, masks, h1, h2, h3, gp_rows, r0, r1, gx, grads=No
     return grads
 
 
-# ---- MADE with BatchNorm1d (use_batch_norm=True): activations kept pre- and post-BatchNorm ------
+# ---- conditioner BatchNorm1d on the any-shape path (MADE use_batch_norm=True, CouplingLayer) ------
+def bn_eval_params(bns, device):
+    """Per BatchNorm [mean, invstd, scale, shift] ([4][H]) from the running statistics (eval
+    mode: nfx_bn_prepare without batch moments)."""
+    out = []
+    for bn in bns:
+        H = bn.num_features
+        t = torch.empty(4, H, device=device, dtype=torch.float32)
+        _lib.checked().nfx_bn_prepare(None, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var,
+                                      float(bn.eps), 0.0, 0, H, t[0], t[1], t[2], t[3], _lib.stream_of(t))
+        out.append(t)
+    return out
+
+
+def bn_train_prepare(z, bn, merge=None):
+    """Train-mode BatchNorm of the pre-activations z: the batch moments (nfx_flowbn_moments), passed
+    to `merge` (the SyncBN merge over ranks) when given, then [mean, invstd, scale, shift] and the
+    running-statistics update (nfx_bn_prepare). Returns (t, stats); stats[0, 0] = the global
+    sample count the batch-statistics backward needs."""
+    L = _lib.checked()
+    B, H = z.shape
+    st = _lib.stream_of(z)
+    ws = torch.empty(max(1, L.nfx_flowbn_workspace_bytes(B, H)), device=z.device, dtype=torch.uint8)
+    stats = torch.empty(H, 3, device=z.device, dtype=torch.float64)
+    L.nfx_flowbn_moments(z, B, H, stats, ws, st)
+    if merge is not None:
+        merge(stats)
+    t = torch.empty(4, H, device=z.device, dtype=torch.float32)
+    L.nfx_bn_prepare(stats, bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, float(bn.eps),
+                     float(bn.momentum), 1, H, t[0], t[1], t[2], t[3], st)
+    torch.autograd.graph.increment_version(bn.running_mean)
+    torch.autograd.graph.increment_version(bn.running_var)
+    return t, stats
+
+
 def bn_apply_relu(z, t):
     """relu(z * scale + shift) with t = [mean, invstd, scale, shift] (nfx_bn_prepare)."""
     h = torch.empty_like(z)
-    _lib.check(_lib.lib().nfx_bn_apply_relu(_lib.ptr(z), _lib.ptr(t[2]), _lib.ptr(t[3]), _lib.ptr(h), z.shape[0],
-                                            z.shape[1], _lib.stream_of(z)), "nfx_bn_apply_relu")
+    _lib.checked().nfx_bn_apply_relu(z, t[2], t[3], h, z.shape[0], z.shape[1], _lib.stream_of(z))
     return h
 
 
@@ -158,19 +187,16 @@ def bn_backward(g, z, t, gamma, train, count, sums_hook=None):
     """dL/dz of BatchNorm + (dL/dgamma, dL/dbeta) as float64 sums; train: batch-statistics terms
     with the global sample count (device float64 pointer `count`), sums passed to `sums_hook`
     (SyncBN all-reduce) first."""
-    L = _lib.lib()
-    M, N = g.shape
+    L = _lib.checked()
+    M, H = g.shape
     st = _lib.stream_of(g)
-    sums = torch.empty(2, N, device=g.device, dtype=torch.float64)
-    ws = torch.empty(max(1, L.nfx_bn_workspace_bytes(M, N)), device=g.device, dtype=torch.uint8)
-    _lib.check(L.nfx_bn_backward_sums(_lib.ptr(g), _lib.ptr(z), _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(sums), M, N,
-                                      _lib.ptr(ws), st), "nfx_bn_backward_sums")
+    sums = torch.empty(2, H, device=g.device, dtype=torch.float64)
+    ws = torch.empty(max(1, L.nfx_bn_workspace_bytes(M, H)), device=g.device, dtype=torch.uint8)
+    L.nfx_bn_backward_sums(g, z, t[0], t[1], sums, M, H, ws, st)
     if train and sums_hook is not None:
         sums_hook(sums)
     gz = torch.empty_like(g)
-    _lib.check(L.nfx_bn_backward_apply(_lib.ptr(g), _lib.ptr(z), _lib.ptr(t[0]), _lib.ptr(t[1]), _lib.ptr(gamma),
-                                       _lib.ptr(sums), _lib.ptr(count) if train else None, int(train), _lib.ptr(gz),
-                                       M, N, st), "nfx_bn_backward_apply")
+    L.nfx_bn_backward_apply(g, z, t[0], t[1], gamma, sums, count if train else None, int(train), gz, M, H, st)
     return gz, sums
 
 

@@ -18,7 +18,7 @@ from torch.nn import functional as F
 
 from .. import _lib
 from . import generic as _generic
-from .flow import HipFlow, STATS
+from .flow import HipFlow, STATS, timed
 
 MAX_K = 11        # 3K-1 <= 32: one MFMA row tile of spline parameters per transformed dim
 MAX_D = 64        # spline_coupling_kernel (d <= 8) / spline_wide_kernel (d <= 64)
@@ -254,9 +254,8 @@ class SplineCouplingLayer(HipFlow):
         xin = x
         if bounds is not None:
             xin = torch.empty_like(x)
-            _lib.check(_lib.lib().nfx_spline_rescale(_lib.ptr(x), _lib.ptr(bounds), _lib.ptr(xin), x.shape[0],
-                                                     self.data_dim, float(self.bound), _lib.stream_of(x)),
-                       "nfx_spline_rescale")
+            _lib.checked().nfx_spline_rescale(x, bounds, xin, x.shape[0], self.data_dim, float(self.bound),
+                                              _lib.stream_of(x))
         h1, h2, prm = _generic.mlp3_forward(xin, self.param_net[0], self.param_net[2], self.param_net[4], mask)
         return mask, xin, h1, h2, prm
 
@@ -267,17 +266,15 @@ class SplineCouplingLayer(HipFlow):
     def _generic_launch(self, x, out, log_det, direction, accumulate):
         bounds = self._bounds(x.device)
         mask, _, _, _, prm = self._generic_params(x, bounds)
-        L = _lib.lib()
+        L = _lib.checked()
         if bounds is None:
-            _lib.check(L.nfx_spline_elem_forward(
-                _lib.ptr(x), _lib.ptr(prm), _lib.ptr(mask), _lib.ptr(out), _lib.ptr(log_det), x.shape[0],
-                self.data_dim, self.num_bins, *self._spline_scalars(), int(direction), int(bool(accumulate)),
-                _lib.stream_of(x)), "nfx_spline_elem_forward")
+            L.nfx_spline_elem_forward(x, prm, mask, out, log_det, x.shape[0], self.data_dim, self.num_bins,
+                                      *self._spline_scalars(), int(direction), int(bool(accumulate)),
+                                      _lib.stream_of(x))
         else:
-            _lib.check(L.nfx_spline_elem_forward_bounded(
-                _lib.ptr(x), _lib.ptr(prm), _lib.ptr(mask), _lib.ptr(bounds), _lib.ptr(out), _lib.ptr(log_det),
-                x.shape[0], self.data_dim, self.num_bins, *self._spline_scalars(), int(direction),
-                int(bool(accumulate)), _lib.stream_of(x)), "nfx_spline_elem_forward_bounded")
+            L.nfx_spline_elem_forward_bounded(x, prm, mask, bounds, out, log_det, x.shape[0], self.data_dim,
+                                              self.num_bins, *self._spline_scalars(), int(direction),
+                                              int(bool(accumulate)), _lib.stream_of(x))
 
     def _generic_backward(self, x, gy, gld, direction):
         """dL/dx and parameter gradients on the any-shape path: conditioner recompute (GEMMs),
@@ -288,18 +285,14 @@ class SplineCouplingLayer(HipFlow):
         mask, xin, h1, h2, prm = self._generic_params(x, bounds)
         gprm = torch.empty_like(prm)
         gx = torch.empty_like(x)
-        L = _lib.lib()
+        L = _lib.checked()
         if bounds is None:
-            _lib.check(L.nfx_spline_elem_backward(
-                _lib.ptr(x), _lib.ptr(prm), _lib.ptr(mask), _lib.ptr(gy), _lib.ptr(gld), _lib.ptr(gprm),
-                _lib.ptr(gx), B, d, self.num_bins, *self._spline_scalars(), int(direction), _lib.stream_of(x)),
-                "nfx_spline_elem_backward")
+            L.nfx_spline_elem_backward(x, prm, mask, gy, gld, gprm, gx, B, d, self.num_bins, *self._spline_scalars(),
+                                       int(direction), _lib.stream_of(x))
             out_scale = None
         else:
-            _lib.check(L.nfx_spline_elem_backward_bounded(
-                _lib.ptr(x), _lib.ptr(prm), _lib.ptr(mask), _lib.ptr(bounds), _lib.ptr(gy), _lib.ptr(gld),
-                _lib.ptr(gprm), _lib.ptr(gx), B, d, self.num_bins, *self._spline_scalars(), int(direction),
-                _lib.stream_of(x)), "nfx_spline_elem_backward_bounded")
+            L.nfx_spline_elem_backward_bounded(x, prm, mask, bounds, gy, gld, gprm, gx, B, d, self.num_bins,
+                                               *self._spline_scalars(), int(direction), _lib.stream_of(x))
             out_scale = bounds[3]
         grads = _generic.mlp3_backward(xin, self.param_net[0], self.param_net[2], self.param_net[4], mask, h1, h2,
                                        gprm, gx, out_scale=out_scale)
@@ -307,12 +300,11 @@ class SplineCouplingLayer(HipFlow):
 
     def _build_pack(self, device):
         d, H, K = self.data_dim, self._hidden(), self.num_bins
-        L = _lib.lib()
+        L = _lib.checked()
         packed = torch.empty(L.nfx_spline_packed_floats(d, H, K), device=device, dtype=torch.float32)
         raw, keep = _lib.mlp_raw([self.param_net[0], self.param_net[2], self.param_net[4]])
-        mask = self.mask.detach().to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(L.nfx_spline_pack(raw, _lib.ptr(mask), d, H, K, _lib.ptr(packed),
-                                     _lib.stream_of(packed)), "nfx_spline_pack")
+        mask = self._mask_dev(device)
+        L.nfx_spline_pack(raw, mask, d, H, K, packed, _lib.stream_of(packed))
         packed._nfx_keep = (keep, mask)
         return packed
 
@@ -341,12 +333,11 @@ class SplineCouplingLayer(HipFlow):
 
     def _build_bwd_pack(self, device):
         d, H, K = self.data_dim, self._hidden(), self.num_bins
-        L = _lib.lib()
+        L = _lib.checked()
         packed = torch.empty(L.nfx_spline_backward_packed_floats(d, H, K), device=device, dtype=torch.float32)
         raw, keep = _lib.mlp_raw([self.param_net[0], self.param_net[2], self.param_net[4]])
-        mask = self.mask.detach().to(device=device, dtype=torch.float32).contiguous()
-        _lib.check(L.nfx_spline_pack_backward(raw, _lib.ptr(mask), d, H, K, _lib.ptr(packed),
-                                              _lib.stream_of(packed)), "nfx_spline_pack_backward")
+        mask = self._mask_dev(device)
+        L.nfx_spline_pack_backward(raw, mask, d, H, K, packed, _lib.stream_of(packed))
         packed._nfx_keep = (keep, mask)
         return packed, mask
 
@@ -362,23 +353,15 @@ class SplineCouplingLayer(HipFlow):
         if not self._fused_backward_ok():
             return self._generic_backward(x, gy, gld, direction)
         packed, mask = self._packed(x.device, self._build_bwd_pack, slot="_nfx_bwd_pack_cache")
-        L = _lib.lib()
+        L = _lib.checked()
         gx = torch.empty_like(x)
         grads = torch.empty(L.nfx_spline_backward_param_floats(d, H, K), device=x.device, dtype=torch.float32)
         ws = torch.empty(L.nfx_spline_backward_workspace_bytes(B, d, H, K), device=x.device, dtype=torch.uint8)
         nt = self._n_transformed()
-        ev = BACKWARD_EVENTS
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        _lib.check(L.nfx_spline_coupling_backward(
-            _lib.ptr(packed), _lib.ptr(mask), _lib.ptr(x), _lib.ptr(gy), _lib.ptr(gld), _lib.ptr(gx),
-            _lib.ptr(grads), _lib.ptr(ws), B, d, H, K, nt, float(self.bound), float(self.min_bin_width),
-            float(self.min_bin_height), float(self.min_derivative), int(direction), _lib.stream_of(x)),
-            "nfx_spline_coupling_backward")
-        if ev is not None:
-            e1.record()
-            ev.append(("spline_bwd_kernel", e0, e1))
+        with timed(BACKWARD_EVENTS, "spline_bwd_kernel"):
+            L.nfx_spline_coupling_backward(packed, mask, x, gy, gld, gx, grads, ws, B, d, H, K, nt, float(self.bound),
+                                           float(self.min_bin_width), float(self.min_bin_height),
+                                           float(self.min_derivative), int(direction), _lib.stream_of(x))
         out, o = [], 0
         for prm in self.parameters():
             n = prm.numel()
@@ -392,24 +375,20 @@ class SplineCouplingLayer(HipFlow):
             return self._generic_launch(x, out, log_det, direction, accumulate)
         packed = self._packed(x.device, self._build_pack)
         rescale, lo, hi = self._rescale_scalars()
-        _lib.check(_lib.lib().nfx_spline_coupling(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), x.shape[0],
-            self.data_dim, self._hidden(), self.num_bins, float(self.bound),
+        _lib.checked().nfx_spline_coupling(
+            packed, x, out, log_det, x.shape[0], self.data_dim, self._hidden(), self.num_bins, float(self.bound),
             float(self.min_bin_width), float(self.min_bin_height), float(self.min_derivative),
-            rescale, lo, hi, int(direction), int(bool(accumulate)), _lib.stream_of(x)),
-            "nfx_spline_coupling")
+            rescale, lo, hi, int(direction), int(bool(accumulate)), _lib.stream_of(x))
 
     def _hip_launch_logprob(self, x, out, log_det, logp, sums, workspace, accumulate):
         if not self._fused_family():
             return False
         packed = self._packed(x.device, self._build_pack)
         rescale, lo, hi = self._rescale_scalars()
-        _lib.check(_lib.lib().nfx_spline_coupling_logprob(
-            _lib.ptr(packed), _lib.ptr(x), _lib.ptr(out), _lib.ptr(log_det), _lib.ptr(logp),
-            _lib.ptr(sums), _lib.ptr(workspace), x.shape[0], self.data_dim, self._hidden(),
-            self.num_bins, float(self.bound), float(self.min_bin_width),
-            float(self.min_bin_height), float(self.min_derivative), rescale, lo, hi,
-            int(bool(accumulate)), _lib.stream_of(x)), "nfx_spline_coupling_logprob")
+        _lib.checked().nfx_spline_coupling_logprob(
+            packed, x, out, log_det, logp, sums, workspace, x.shape[0], self.data_dim, self._hidden(),
+            self.num_bins, float(self.bound), float(self.min_bin_width), float(self.min_bin_height),
+            float(self.min_derivative), rescale, lo, hi, int(bool(accumulate)), _lib.stream_of(x))
         return True
 
 
@@ -431,20 +410,17 @@ def chain_ok(flows, x):
 def chain_launch(flows, x, out, ld, direction, accumulate, logprob=None):
     """All `flows` (module order) in one nfx_spline_chain launch; logprob=(logp, sums, workspace)
     adds the fused Gaussian log-density to an inverse chain."""
-    packs = (ctypes.c_void_p * len(flows))(*[_lib.ptr(f._packed(x.device, f._build_pack)) for f in flows])
+    packs = (ctypes.c_void_p * len(flows))(*[f._packed(x.device, f._build_pack).data_ptr() for f in flows])
     f0 = flows[0]
-    L = _lib.lib()
-    p = _lib.ptr
+    L = _lib.checked()
     consts = (float(f0.bound), float(f0.min_bin_width), float(f0.min_bin_height), float(f0.min_derivative))
     if logprob is not None:
         logp, sums, ws = logprob
-        _lib.check(L.nfx_spline_chain_logprob(packs, len(flows), p(x), p(out), p(ld), p(logp), p(sums), p(ws),
-                                              x.shape[0], f0.data_dim, f0._hidden(), f0.num_bins, *consts,
-                                              int(bool(accumulate)), _lib.stream_of(x)), "nfx_spline_chain_logprob")
+        L.nfx_spline_chain_logprob(packs, len(flows), x, out, ld, logp, sums, ws, x.shape[0], f0.data_dim,
+                                   f0._hidden(), f0.num_bins, *consts, int(bool(accumulate)), _lib.stream_of(x))
     else:
-        _lib.check(L.nfx_spline_chain(packs, len(flows), p(x), p(out), p(ld), x.shape[0], f0.data_dim, f0._hidden(),
-                                      f0.num_bins, *consts, int(direction), int(bool(accumulate)), _lib.stream_of(x)),
-                   "nfx_spline_chain")
+        L.nfx_spline_chain(packs, len(flows), x, out, ld, x.shape[0], f0.data_dim, f0._hidden(), f0.num_bins,
+                           *consts, int(direction), int(bool(accumulate)), _lib.stream_of(x))
     STATS["hip"] += 1
 
 
@@ -481,13 +457,12 @@ def _chain_key_ok(flows, x):
 def chain_sample(flows, rng_state, seed, z, x, ld):
     """z ~ N(0, I) drawn on the device and x, ld = forward(z) through every flow, one launch
     (nfx_spline_chain_sample); rng_state = the device uint64[2] generator state it advances."""
-    packs = (ctypes.c_void_p * len(flows))(*[_lib.ptr(f._packed(x.device, f._build_pack)) for f in flows])
+    packs = (ctypes.c_void_p * len(flows))(*[f._packed(x.device, f._build_pack).data_ptr() for f in flows])
     f0 = flows[0]
-    p = _lib.ptr
-    _lib.check(_lib.lib().nfx_spline_chain_sample(
-        packs, len(flows), int(seed) & ((1 << 64) - 1), p(rng_state), p(z), p(x), p(ld), x.shape[0], f0.data_dim,
+    _lib.checked().nfx_spline_chain_sample(
+        packs, len(flows), int(seed) & ((1 << 64) - 1), rng_state, z, x, ld, x.shape[0], f0.data_dim,
         f0._hidden(), f0.num_bins, float(f0.bound), float(f0.min_bin_width), float(f0.min_bin_height),
-        float(f0.min_derivative), _lib.stream_of(x)), "nfx_spline_chain_sample")
+        float(f0.min_derivative), _lib.stream_of(x))
     STATS["hip"] += 1
 
 
@@ -585,10 +560,8 @@ def _rqs_unit_hip(inputs, widths, heights, derivatives, min_w, min_h, min_d, inv
     uw, uh, ud = widths.contiguous(), heights.contiguous(), derivatives.contiguous()
     out = torch.empty_like(x)
     ld = torch.empty_like(x)
-    _lib.check(_lib.lib().nfx_rqs_unit(
-        _lib.ptr(x), _lib.ptr(uw), _lib.ptr(uh), _lib.ptr(ud), _lib.ptr(out), _lib.ptr(ld), N, K,
-        float(min_w), float(min_h), float(min_d), int(bool(inverse)), _lib.stream_of(x)),
-        "nfx_rqs_unit")
+    _lib.checked().nfx_rqs_unit(x, uw, uh, ud, out, ld, N, K, float(min_w), float(min_h), float(min_d),
+                                int(bool(inverse)), _lib.stream_of(x))
     STATS["hip"] += 1
     return out, ld
 
@@ -617,10 +590,8 @@ class _RqsUnitFn(torch.autograd.Function):
         go = torch.zeros_like(x) if g_out is None else g_out.reshape(-1).contiguous().float()
         gl = torch.zeros_like(x) if g_ld is None else g_ld.reshape(-1).contiguous().float()
         gx, gw, gh, gd = torch.empty_like(x), torch.empty_like(uw), torch.empty_like(uh), torch.empty_like(ud)
-        p = _lib.ptr
-        _lib.check(_lib.lib().nfx_rqs_unit_backward(
-            p(x), p(uw), p(uh), p(ud), p(go), p(gl), p(gx), p(gw), p(gh), p(gd), N, K, min_w, min_h, min_d,
-            int(inverse), _lib.stream_of(x)), "nfx_rqs_unit_backward")
+        _lib.checked().nfx_rqs_unit_backward(x, uw, uh, ud, go, gl, gx, gw, gh, gd, N, K, min_w, min_h, min_d,
+                                             int(inverse), _lib.stream_of(x))
         STATS["hip"] += 1
         S = ctx.S
         return gx.view(S), gw.view(S + (K,)), gh.view(S + (K,)), gd.view(S + (K - 1,)), None

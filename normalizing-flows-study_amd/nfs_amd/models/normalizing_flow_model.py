@@ -325,9 +325,8 @@ class NormalizingFlowModel(nn.Module):
         f0 = self.flows[0]
         cur = x if (n - 1) % 2 == 0 else spare
         packed = f0._packed(dev, f0._build_pack)
-        _lib.check(_lib.lib().nfx_made_affine_sample(
-            _lib.ptr(packed), seed & ((1 << 64) - 1), _lib.ptr(state), _lib.ptr(z), _lib.ptr(cur), _lib.ptr(ld),
-            num_samples, d, f0.conditioner.hidden_dim, _lib.stream_of(x)), "nfx_made_affine_sample")
+        _lib.checked().nfx_made_affine_sample(packed, seed & ((1 << 64) - 1), state, z, cur, ld, num_samples, d,
+                                              f0.conditioner.hidden_dim, _lib.stream_of(x))
         STATS["hip"] += 1
         with torch.no_grad():
             for i in range(1, n):
@@ -362,8 +361,7 @@ class NormalizingFlowModel(nn.Module):
         z = torch.empty(num_samples, d, device=dev) if out is None else out[0]
         if z.shape != (num_samples, d) or z.dtype != torch.float32 or z.device != dev or not z.is_contiguous():
             raise ValueError(f"sample_on_device: z must be a contiguous fp32 [{num_samples}, {d}] tensor on {dev}")
-        _lib.check(_lib.lib().nfx_base_normal(seed & ((1 << 64) - 1), _lib.ptr(state), _lib.ptr(z), num_samples, d,
-                                              _lib.stream_of(z)), "nfx_base_normal")
+        _lib.checked().nfx_base_normal(seed & ((1 << 64) - 1), state, z, num_samples, d, _lib.stream_of(z))
         STATS["hip"] += 1
         with torch.no_grad():
             x, ld = self._hip_chain(z, 1)
@@ -425,7 +423,7 @@ def new_gauss_workspace(B, device):
     stream), so even the first call skips the kernels' one-time claim of a foreign word."""
     ws = torch.empty(_lib.lib().nfx_gauss_workspace_bytes(B), device=device, dtype=torch.uint8)
     if ws.device.type == "cuda":
-        _lib.check(_lib.lib().nfx_gauss_workspace_init(_lib.ptr(ws), _lib.stream_of(ws)), "nfx_gauss_workspace_init")
+        _lib.checked().nfx_gauss_workspace_init(ws, _lib.stream_of(ws))
     return ws
 
 
@@ -444,10 +442,8 @@ def gauss_logprob(z, ld, logp=None, sums=None, ws=None):
         logp = torch.empty(B, device=z.device, dtype=torch.float32)
     if sums is None:
         sums = torch.empty(2, device=z.device, dtype=torch.float64)
-    L = _lib.lib()
     ws = gauss_workspace(B, z.device) if ws is None else check_gauss_workspace(ws, B, z.device)
-    _lib.check(L.nfx_gauss_logprob(_lib.ptr(z), _lib.ptr(ld), _lib.ptr(logp), _lib.ptr(sums),
-                                   _lib.ptr(ws), B, d, _lib.stream_of(z)), "nfx_gauss_logprob")
+    _lib.checked().nfx_gauss_logprob(z, ld, logp, sums, ws, B, d, _lib.stream_of(z))
     STATS["hip"] += 1
     return logp, sums
 
@@ -470,8 +466,7 @@ class _GaussLogProbFn(torch.autograd.Function):
         B, d = z.shape
         g = g.contiguous().float()
         gz, gld = torch.empty_like(z), torch.empty_like(g)
-        _lib.check(_lib.lib().nfx_gauss_logprob_backward(_lib.ptr(z), _lib.ptr(g), _lib.ptr(gz), _lib.ptr(gld), B, d,
-                                                         _lib.stream_of(z)), "nfx_gauss_logprob_backward")
+        _lib.checked().nfx_gauss_logprob_backward(z, g, gz, gld, B, d, _lib.stream_of(z))
         STATS["hip"] += 1
         return gz, gld, None
 
@@ -486,17 +481,11 @@ def _bn_hip_ok(x):
     return x.device.type == "cuda" and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] <= _FLOWBN_MAX_D
 
 
-def _bn_ptrs(bn):
-    return (_lib.ptr(bn.weight), _lib.ptr(bn.bias), _lib.ptr(bn.running_mean), _lib.ptr(bn.running_var))
-
-
 def _bn_launch(bn, x, out, ld, direction):
     """out = BN affine of x (running statistics), ld -+= the scalar log-det, in place."""
     B, d = x.shape
-    w, b, rm, rv = _bn_ptrs(bn)
-    _lib.check(_lib.lib().nfx_flowbn_apply(_lib.ptr(x), _lib.ptr(out), _lib.ptr(ld), w, b, rm, rv,
-                                           float(bn.eps), B, d, direction, _lib.stream_of(x)),
-               "nfx_flowbn_apply")
+    _lib.checked().nfx_flowbn_apply(x, out, ld, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps),
+                                    B, d, direction, _lib.stream_of(x))
     STATS["hip"] += 1
 
 
@@ -509,17 +498,15 @@ def _bn_update_running_hip(bn, x):
     statistics; with SyncBN enabled the moments are those of every rank's shard."""
     x = x.detach().contiguous()
     B, d = x.shape
-    L = _lib.lib()
+    L = _lib.checked()
     stats = torch.empty(d, 3, device=x.device, dtype=torch.float64)
     ws = _bn_workspace(B, d, x.device)
     st = _lib.stream_of(x)
-    _lib.check(L.nfx_flowbn_moments(_lib.ptr(x), B, d, _lib.ptr(stats), _lib.ptr(ws), st), "nfx_flowbn_moments")
+    L.nfx_flowbn_moments(x, B, d, stats, ws, st)
     merge_bn_stats(stats)
     momentum = bn.momentum if bn.momentum is not None else 0.1
     with torch.no_grad():
-        _lib.check(L.nfx_flowbn_update_running(_lib.ptr(stats), _lib.ptr(bn.running_mean),
-                                               _lib.ptr(bn.running_var), float(momentum), d, st),
-                   "nfx_flowbn_update_running")
+        L.nfx_flowbn_update_running(stats, bn.running_mean, bn.running_var, float(momentum), d, st)
         # the kernel writes the buffers behind autograd's back; bump their versions so every
         # version-keyed cache (packed images, graph strict checks) sees the change
         torch.autograd.graph.increment_version(bn.running_mean)
@@ -569,9 +556,7 @@ class _FlowBatchNormFn(torch.autograd.Function):
         gy = gy.contiguous() if gy is not None else None
         gld_c = gld.contiguous() if gld is not None else None
         ws = _bn_workspace(B, d, x.device)
-        _lib.check(_lib.lib().nfx_flowbn_backward(
-            _lib.ptr(x), _lib.ptr(gy), _lib.ptr(gld_c), _lib.ptr(gx), _lib.ptr(weight.detach()),
-            _lib.ptr(bias.detach()), _lib.ptr(rm), _lib.ptr(rv), ctx.eps, _lib.ptr(dg), _lib.ptr(db), B, d,
-            ctx.direction, _lib.ptr(ws), _lib.stream_of(x)), "nfx_flowbn_backward")
+        _lib.checked().nfx_flowbn_backward(x, gy, gld_c, gx, weight.detach(), bias.detach(), rm, rv, ctx.eps, dg, db,
+                                           B, d, ctx.direction, ws, _lib.stream_of(x))
         STATS["hip"] += 1
         return gx, gld, dg, db, None, None
