@@ -654,6 +654,49 @@ int nfx_cnf_supported(int64_t B, int d, int H);
 int nfx_cnf_integrate(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,
                       int H, float t_begin, float t_end, float step_size, int accumulate, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ContinuousFlow backward: the gradients of the DISCRETE solve above (what autograd gives for the
+ * scheme, not the adjoint ODE) for 1 <= d <= 8 and H in {32, 64} (nfx_cnf_backward_supported: 1
+ * inside the family, host-only; H = 128 is outside it).
+ *   nfx_cnf_pack_backward      the backward's weight image, nfx_cnf_backward_packed_floats floats.
+ *                              It BEGINS with the forward image, so the same buffer serves
+ *                              nfx_cnf_integrate / nfx_cnf_integrate_save.
+ *   nfx_cnf_integrate_save     nfx_cnf_integrate (bit-identical out and log_det) that also writes
+ *                              traj, nfx_cnf_trajectory_floats floats: the state at the start of
+ *                              steps 1 .. n-1, step-major [n-1][B][d], then the last step's result
+ *                              before the guards, y_n [B][d] and its log-det [B]. Equal times: 0
+ *                              floats, traj may be null.
+ *   nfx_cnf_backward           gx [B, d] and the six parameter gradients in nn.Linear layout (gw1
+ *                              [H, d+1], gb1 [H], gw2 [H, H], gb2 [H], gw3 [d, H], gb3 [d];
+ *                              overwritten, not accumulated) from the cotangents gy [B, d] and gld
+ *                              [B] of (out, log_det), the forward's input `in`, its trajectory and the
+ *                              raw w1, w2, w3. workspace: nfx_cnf_backward_workspace_floats floats,
+ *                              any content. Three launches: the sweep (one wave per 32-row tile up to
+ *                              nfx_cnf_backward_slots waves, nfx_cnf_backward_block_threads threads per
+ *                              workgroup; each wave leaves its partial sums in its own workspace
+ *                              slot), the slot reduction in index order, and the finish. No atomics:
+ *                              the same call twice gives the same bits.
+ * The clamp of out and log_det passes the cotangent where the unclamped value lies in [-10, 10]
+ * (bounds included, as torch.clamp). A row whose input or final state holds a non-finite value
+ * contributes nothing to any parameter gradient and gets gx = gy. Equal times: gx = gy, zero
+ * parameter gradients. gx must not alias gy or in.
+ * ------------------------------------------------------------------------------------- */
+int nfx_cnf_backward_supported(int64_t B, int d, int H);
+size_t nfx_cnf_backward_packed_floats(int d, int H);
+size_t nfx_cnf_trajectory_floats(int64_t B, int d, float t_begin, float t_end, float step_size);
+size_t nfx_cnf_backward_workspace_floats(int64_t B, int d, int H);
+size_t nfx_cnf_backward_slots(int64_t B, int d, int H);
+size_t nfx_cnf_backward_block_threads(int64_t B, int d, int H);
+int nfx_cnf_pack_backward(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                          const float* b3, int d, int H, float* packed, void* stream);
+int nfx_cnf_integrate_save(const float* packed, const float* in, float* out, float* log_det, float* traj,
+                           int64_t B, int d, int H, float t_begin, float t_end, float step_size, int accumulate,
+                           void* stream);
+int nfx_cnf_backward(const float* packed, const float* w1, const float* w2, const float* w3, const float* in,
+                     const float* traj, const float* gy, const float* gld, float* gx, float* gw1, float* gb1,
+                     float* gw2, float* gb2, float* gw3, float* gb3, float* workspace, int64_t B, int d, int H,
+                     float t_begin, float t_end, float step_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

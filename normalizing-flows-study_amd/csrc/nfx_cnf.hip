@@ -32,6 +32,10 @@ template <>
 cnf_kernel_t cnf_pick_ht<2>(int d);
 template <>
 cnf_kernel_t cnf_pick_ht<4>(int d);
+template <>
+cnf_kernel_t cnf_save_pick_ht<1>(int d);
+template <>
+cnf_kernel_t cnf_save_pick_ht<2>(int d);
 
 static cnf_kernel_t pick_cnf(int d, int H) {
     switch (H) {
@@ -108,33 +112,29 @@ extern "C" int nfx_cnf_pack(const float* w1, const float* b1, const float* w2, c
     return check_launch("cnf_pack_kernel");
 }
 
-extern "C" int nfx_cnf_integrate(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,
-                                 int H, float t_begin, float t_end, float step_size, int accumulate, void* stream) {
+// One launch of the solve; `save` picks the instantiation that also writes the trajectory (H <= 64).
+static int cnf_launch(bool save, const float* packed, const float* in, float* out, float* log_det, float* traj,
+                      int64_t B, int d, int H, float t_begin, float t_end, float step_size, int accumulate,
+                      void* stream) {
     if (B < 0 || d <= 0 || H <= 0) return set_error(NFX_EINVAL, "cnf: bad shape B=%lld d=%d H=%d", (long long)B, d, H);
     if (!(step_size > 0.f) || !isfinite(step_size) || !isfinite(t_begin) || !isfinite(t_end))
         return set_error(NFX_EINVAL, "cnf: times must be finite and step_size positive");
-    cnf_kernel_t k = pick_cnf(d, H);
-    if (!k) return set_error(NFX_EUNSUPPORTED, "cnf: d=%d H=%d outside the compiled family (d<=8, H in {32,64,128})", d, H);
+    cnf_kernel_t k = save ? (H == 32 ? cnf_save_pick_ht<1>(d) : H == 64 ? cnf_save_pick_ht<2>(d) : nullptr)
+                          : pick_cnf(d, H);
+    if (!k)
+        return set_error(NFX_EUNSUPPORTED, "cnf: d=%d H=%d outside the compiled family (d<=8, H in %s)", d, H,
+                         save ? "{32,64}" : "{32,64,128}");
     CnfArgs A{};
-    // The ascending grid of the fixed-step solver, in fp32 like the times tensor: n = ceil((s1 - s0)
-    // / h + 1) points s_k = k h + s0 with the last one pinned to s1. A decreasing interval is the
-    // negated-time problem (s = -t): the same grid walked downward with negative dt.
-    A.sgn = t_begin <= t_end ? 1.f : -1.f;
-    A.s0 = A.sgn * t_begin;
-    A.s1 = A.sgn * t_end;
-    A.h = step_size;
-    if (t_begin != t_end) {
-        const float n = ceilf((A.s1 - A.s0) / step_size + 1.f);  // fp32 throughout, as the composite
-        if (!(n <= 16777216.f)) return set_error(NFX_EINVAL, "cnf: too many steps");
-        A.nsteps = (int)n - 1;
-    }
+    if (!cnf_grid(t_begin, t_end, step_size, A)) return set_error(NFX_EINVAL, "cnf: too many steps");
     if (B == 0) return NFX_OK;
-    if (!packed || !in || !out || !log_det) return set_error(NFX_EINVAL, "cnf: null pointer");
+    if (!packed || !in || !out || !log_det || (save && A.nsteps > 0 && !traj))
+        return set_error(NFX_EINVAL, "cnf: null pointer");
     if (in == out) return set_error(NFX_EINVAL, "cnf: in and out must not alias");
     A.packed = packed;
     A.in = in;
     A.out = out;
     A.logdet = log_det;
+    A.traj = traj;
     A.B = B;
     A.ntiles = (B + 31) / 32;
     A.accumulate = accumulate ? 1 : 0;
@@ -148,5 +148,25 @@ extern "C" int nfx_cnf_integrate(const float* packed, const float* in, float* ou
     if (rc) return rc;
     const int grid = resident_grid((const void*)k, threads, lds, (A.ntiles + nw - 1) / nw);
     k<<<grid, threads, lds, (hipStream_t)stream>>>(A);
-    return check_launch("cnf_kernel");
+    return check_launch(save ? "cnf_save_kernel" : "cnf_kernel");
+}
+
+extern "C" int nfx_cnf_integrate(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,
+                                 int H, float t_begin, float t_end, float step_size, int accumulate, void* stream) {
+    return cnf_launch(false, packed, in, out, log_det, nullptr, B, d, H, t_begin, t_end, step_size, accumulate,
+                      stream);
+}
+
+extern "C" int nfx_cnf_integrate_save(const float* packed, const float* in, float* out, float* log_det, float* traj,
+                                      int64_t B, int d, int H, float t_begin, float t_end, float step_size,
+                                      int accumulate, void* stream) {
+    return cnf_launch(true, packed, in, out, log_det, traj, B, d, H, t_begin, t_end, step_size, accumulate, stream);
+}
+
+extern "C" size_t nfx_cnf_trajectory_floats(int64_t B, int d, float t_begin, float t_end, float step_size) {
+    CnfArgs A{};
+    if (B <= 0 || d <= 0 || !(step_size > 0.f) || !isfinite(step_size) || !isfinite(t_begin) || !isfinite(t_end) ||
+        !cnf_grid(t_begin, t_end, step_size, A))
+        return 0;
+    return cnf_traj_floats(B, d, A.nsteps);
 }

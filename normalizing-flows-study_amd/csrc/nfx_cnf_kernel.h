@@ -2,6 +2,8 @@
 //   dz/dt = v(z, t),  dl/dt = +tr(dv/dz),   v = W3 tanh(W2 tanh(W1 [z; t] + b1) + b2) + b3
 // in ONE launch (see nfx_cnf.hip for the design notes and the cost model).
 #pragma once
+#include <math.h>
+
 #include "nfx_common.h"
 
 namespace nfx {
@@ -49,7 +51,33 @@ struct CnfArgs {
     int nsteps;         // grid points - 1; 0: equal times, the identity
     float s0, s1, h;    // ascending grid s_k = k h + s0, last point s1
     float sgn;          // t = sgn * s: -1 walks the grid downward (t_begin > t_end)
+    float* traj;        // SAVE instantiations only: the trajectory the fused backward replays
 };
+
+// The ascending grid of the fixed-step solver, in fp32 like the times tensor: n = ceil((s1 - s0)
+// / h + 1) points s_k = k h + s0 with the last one pinned to s1. A decreasing interval is the
+// negated-time problem (s = -t): the same grid walked downward with negative dt. Fills sgn, s0,
+// s1, h, nsteps; false when the grid has too many points.
+inline bool cnf_grid(float t_begin, float t_end, float step_size, CnfArgs& A) {
+    A.sgn = t_begin <= t_end ? 1.f : -1.f;
+    A.s0 = A.sgn * t_begin;
+    A.s1 = A.sgn * t_end;
+    A.h = step_size;
+    A.nsteps = 0;
+    if (t_begin != t_end) {
+        const float n = ceilf((A.s1 - A.s0) / step_size + 1.f);  // fp32 throughout, as the composite
+        if (!(n <= 16777216.f)) return false;
+        A.nsteps = (int)n - 1;
+    }
+    return true;
+}
+
+// Trajectory of a SAVE launch (floats), nsteps = n >= 1: y_1 .. y_{n-1} step-major [n-1][B][d]
+// (the state at the start of steps 1 .. n-1; y_0 is the input), then the last step's result before
+// the guards, y_n [B][d] and its log-det [B]: the backward's clamp masks read those.
+inline size_t cnf_traj_floats(int64_t B, int d, int nsteps) {
+    return nsteps > 0 ? (size_t)nsteps * (size_t)B * d + (size_t)B : 0;
+}
 
 constexpr int kCnfMaxD = 8;
 
@@ -57,7 +85,7 @@ constexpr int kCnfMaxD = 8;
 // outer-loop spills at H = 64, d >= 6), one for H = 128 (the register file to itself, no scratch).
 constexpr int cnf_waves_per_simd(int HT) { return HT <= 2 ? 2 : 1; }
 
-template <int HT, int D>
+template <int HT, int D, bool SAVE = false>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT)))) void cnf_kernel(CnfArgs A) {
     constexpr CnfLayout L = cnf_layout(D, HT);
@@ -184,6 +212,13 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
             const float sk1 = k + 1 == A.nsteps ? A.s1 : (float)(k + 1) * A.h + A.s0;
             const float t0 = A.sgn * sk, t1 = A.sgn * sk1;
             const float dt = t1 - t0;
+            if constexpr (SAVE) {
+                if (k > 0 && live && h == 0) {
+                    float* tj = A.traj + ((int64_t)(k - 1) * A.B + srow) * D;
+#pragma unroll
+                    for (int j = 0; j < D; ++j) tj[j] = y[j];
+                }
+            }
             float k1[D], k2[D], k3[D], zin[D];
             float l1 = 0.f, l2 = 0.f, l3 = 0.f;
             float t = t0;
@@ -233,6 +268,14 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
             }
         }
 
+        if constexpr (SAVE) {
+            if (live && h == 0 && A.nsteps > 0) {
+                float* tj = A.traj + ((int64_t)(A.nsteps - 1) * A.B + srow) * D;
+#pragma unroll
+                for (int j = 0; j < D; ++j) tj[j] = y[j];
+                A.traj[(int64_t)A.nsteps * A.B * D + srow] = ld;
+            }
+        }
         if (live && h == 0) {
             float o[D];
             float lo = ld;
@@ -261,6 +304,14 @@ cnf_kernel_t cnf_pick_ht(int d);
 template <int HT>
 cnf_kernel_t cnf_pick(int d) {
     return pick_range<1, kCnfMaxD>(d, [](auto D) -> cnf_kernel_t { return cnf_kernel<HT, D()>; });
+}
+
+// The trajectory-saving instantiations (H <= 64), defined in nfx_cnf_bwd_h{1,2}.hip.
+template <int HT>
+cnf_kernel_t cnf_save_pick_ht(int d);
+template <int HT>
+cnf_kernel_t cnf_save_pick(int d) {
+    return pick_range<1, kCnfMaxD>(d, [](auto D) -> cnf_kernel_t { return cnf_kernel<HT, D(), true>; });
 }
 
 }  // namespace nfx

@@ -131,6 +131,15 @@ _SIGNATURES = {
     "nfx_cnf_pack": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "nfx_cnf_supported": (_int, [_i64, _int, _int]),
     "nfx_cnf_integrate": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _f, _f, _f, _int, _vp]),
+    "nfx_cnf_backward_supported": (_int, [_i64, _int, _int]),
+    "nfx_cnf_backward_packed_floats": (_sz, [_int, _int]),
+    "nfx_cnf_trajectory_floats": (_sz, [_i64, _int, _f, _f, _f]),
+    "nfx_cnf_backward_workspace_floats": (_sz, [_i64, _int, _int]),
+    "nfx_cnf_backward_slots": (_sz, [_i64, _int, _int]),
+    "nfx_cnf_backward_block_threads": (_sz, [_i64, _int, _int]),
+    "nfx_cnf_pack_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
+    "nfx_cnf_integrate_save": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _f, _f, _f, _int, _vp]),
+    "nfx_cnf_backward": (_int, [_vp] * 16 + [_i64, _int, _int, _f, _f, _f, _vp]),
     "nfx_rqs_unit": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int,
                                      _vp]),
@@ -200,7 +209,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # every other c_int symbol returns a status, which the checked handle turns into NfxError.
 _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
-    "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_made_sample_supported"))
+    "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
+    "nfx_made_sample_supported"))
 
 
 _as_pointer = _vp.from_param  # (an int as a full-width pointer argument, without a c_void_p object)

@@ -25,7 +25,11 @@ are not reproduced: a fixed-step solver does not raise.)
 
 On a ROCm device the whole integration of a call is ONE gfx950 kernel (csrc/nfx_cnf*.hip) for
 dim <= 8 and hidden_dim in {32, 64, 128}; other shapes raise NotImplementedError there (or run the
-composite with ALLOW_TORCH_FALLBACK). Gradients recompute through the torch composite on the GPU.
+composite with ALLOW_TORCH_FALLBACK). Gradients recompute through the torch composite on the GPU by
+default; with `ContinuousFlow.fused_backward = True` (on the class or an instance) they come from
+the fused reverse sweep of the discrete scheme (csrc/nfx_cnf_bwd*.hip: a trajectory-saving forward,
+the sweep, a fixed-order reduction) for dim <= 8 and hidden_dim in {32, 64}, in HIP only;
+hidden_dim = 128 keeps the composite route. Double backward is not supported there.
 """
 import torch
 import torch.nn as nn
@@ -101,6 +105,9 @@ class ContinuousFlow(HipFlow):
     `dim` (see ODEFunc for that one deliberate difference from the reference)."""
 
     step_size = 0.01  # options={'step_size': 0.01}; a class attribute, the signature stays the reference's
+    # True: gradients come from the fused backward kernels (csrc/nfx_cnf_bwd*.hip) for dim <= 8 and
+    # hidden_dim in {32, 64}; False (the default) recomputes through the composite on the GPU.
+    fused_backward = False
 
     def __init__(self, dim, hidden_dim=64):
         super().__init__()
@@ -188,3 +195,92 @@ class ContinuousFlow(HipFlow):
         _lib.checked().nfx_cnf_integrate(
             packed, x, out, log_det, x.shape[0], self.dim, self.hidden_dim, float(times[0]), float(times[1]),
             float(torch.tensor(self.step_size)), int(bool(accumulate)), _lib.stream_of(x))
+
+    # -- fused backward (opt-in: ContinuousFlow.fused_backward = True) -----------------------------
+    def _dispatch(self, x, direction):
+        if (self.fused_backward and torch.is_grad_enabled() and self._route(x) == "hip"
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+                and self._hip_backward_ok(x, direction)):
+            return _CnfFunction.apply(self, direction, x, *list(self.parameters()))
+        return super()._dispatch(x, direction)
+
+    def _hip_backward_ok(self, x, direction):
+        """The fused backward is switched on and has kernels for this shape (dim <= 8, hidden_dim in
+        {32, 64}); otherwise the gradients recompute through the composite."""
+        return bool(self.fused_backward and x.dim() == 2 and x.shape[1] == self.dim and x.shape[0] >= 1
+                    and _lib.lib().nfx_cnf_backward_supported(x.shape[0], self.dim, self.hidden_dim))
+
+    def _build_backward_pack(self, device):
+        L = _lib.checked()
+        d, H = self.dim, self.hidden_dim
+        packed = torch.empty(L.nfx_cnf_backward_packed_floats(d, H), device=device, dtype=torch.float32)
+        L.nfx_cnf_pack_backward(*self._raw_weights(device), d, H, packed, _lib.stream_of(packed))
+        return packed
+
+    def _raw_weights(self, device):
+        return [p.detach().to(device=device, dtype=torch.float32).contiguous()
+                for lin in self.ode_func.linears() for p in (lin.weight, lin.bias)]
+
+    def _time_args(self, direction):
+        times = self._times(direction).float()
+        return float(times[0]), float(times[1]), float(torch.tensor(self.step_size))
+
+    def _hip_forward_save(self, x, direction):
+        """(y, ld, traj): the forward kernel's outputs, bit for bit, and the trajectory the backward
+        replays (the state at the start of every step, and the unclamped final state)."""
+        L = _lib.checked()
+        x = x.contiguous()
+        B, d, H = x.shape[0], self.dim, self.hidden_dim
+        t0, t1, step = self._time_args(direction)
+        packed = self._packed(x.device, self._build_backward_pack, slot="_nfx_bwd_pack_cache")
+        out = torch.empty_like(x)
+        ld = torch.empty(B, device=x.device, dtype=torch.float32)
+        traj = torch.empty(L.nfx_cnf_trajectory_floats(B, d, t0, t1, step), device=x.device, dtype=torch.float32)
+        L.nfx_cnf_integrate_save(packed, x, out, ld, traj, B, d, H, t0, t1, step, 0, _lib.stream_of(x))
+        return out, ld, traj
+
+    def _hip_backward(self, x, gy, gld, direction, traj=None):
+        """(gx, [gW1, gb1, gW2, gb2, gW3, gb3]) in HIP only; `traj` is the saving forward's
+        trajectory (recomputed here when the caller kept none)."""
+        L = _lib.checked()
+        x = x.contiguous()
+        B, d, H = x.shape[0], self.dim, self.hidden_dim
+        if traj is None:
+            traj = self._hip_forward_save(x, direction)[2]
+        t0, t1, step = self._time_args(direction)
+        packed = self._packed(x.device, self._build_backward_pack, slot="_nfx_bwd_pack_cache")
+        w1, _, w2, _, w3, _ = raw = self._raw_weights(x.device)
+        gy = gy.to(torch.float32).contiguous()
+        gld = gld.to(torch.float32).contiguous()
+        gx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in raw]
+        ws = torch.empty(L.nfx_cnf_backward_workspace_floats(B, d, H), device=x.device, dtype=torch.float32)
+        L.nfx_cnf_backward(packed, w1, w2, w3, x, traj, gy, gld, gx, *grads, ws, B, d, H, t0, t1, step,
+                           _lib.stream_of(x))
+        return gx, grads
+
+
+class _CnfFunction(torch.autograd.Function):
+    """ContinuousFlow with the fused backward: the trajectory-saving forward kernel, then the reverse
+    sweep in HIP. No composite anywhere; double backward is not supported."""
+
+    @staticmethod
+    def forward(ctx, layer, direction, x, *params):
+        from . import flow as _flow
+        _flow.STATS["hip"] += 1
+        with torch.no_grad():
+            y, ld, traj = layer._hip_forward_save(x.detach(), direction)
+        ctx.layer, ctx.direction = layer, direction
+        ctx.save_for_backward(x, traj)
+        return y, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, gld):
+        from . import flow as _flow
+        x, traj = ctx.saved_tensors
+        layer = ctx.layer
+        _flow.STATS["hip"] += 1
+        gx, gparams = layer._hip_backward(x.detach(), gy, gld, ctx.direction, traj)
+        gparams = [g if p.requires_grad else None for p, g in zip(layer.parameters(), gparams)]
+        return (None, None, gx, *gparams)

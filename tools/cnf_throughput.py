@@ -3,6 +3,11 @@
 composite on the same device.
 
     python tools/cnf_throughput.py [--batches 4096,1048576] [--replays 20] [--out FILE.json]
+    python tools/cnf_throughput.py --train [--batches 4096,65536]     # -> profiles/cnf_train.json
+
+`--train` times one NLL step (forward + backward) with the fused backward kernels
+(`ContinuousFlow.fused_backward = True`) against the default route, whose backward recomputes
+through the composite, in the same run; it also reports the backward's cost in forwards.
 
 Per batch size and direction (inverse = density, forward = sampling): hipEvent time of each of
 `--replays` calls after warm-up (median and min), samples/s, and the achieved fp32 MFMA rate from
@@ -58,9 +63,69 @@ def time_calls(fn, warmup, replays):
     return ms
 
 
+def time_steps(fn, warmup, replays):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(replays):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
+def train(a):
+    """One NLL step (forward + backward, no optimizer) of ContinuousFlow(d, H): the fused backward
+    (fused_backward = True) against the composite recompute (the default route), in the same run."""
+    dev = torch.device("cuda:0")
+    d, H = a.dim, a.hidden
+    rows = []
+    for B in [int(b) for b in (a.batches or "4096,65536").split(",")]:
+        x = 1.5 * torch.randn(B, d, generator=torch.Generator().manual_seed(B)).to(dev)
+        row = {"B": B}
+        for name, fused, replays in (("fused", True, a.replays), ("composite", False, a.eager_replays)):
+            flow = make_flow(d, H, dev)
+            flow.fused_backward = fused
+            model = nfs_amd.NormalizingFlowModel([flow]).to(dev)
+
+            def step():
+                model.zero_grad(set_to_none=True)
+                (-model.log_prob(x).mean()).backward()
+
+            nfs_amd.reset_stats()
+            ms = time_steps(step, 1 if not fused else a.warmup, replays)
+            assert nfs_amd.STATS["torch"] == (0 if fused else 1 + replays), nfs_amd.STATS
+            row[f"{name}_step_ms_median"], row[f"{name}_step_ms_min"] = statistics.median(ms), min(ms)
+            if fused:  # the forward alone, for the backward's cost in forwards
+                fms = time_calls(lambda: flow.inverse(x), a.warmup, a.replays)
+                row["fused_forward_ms_median"] = statistics.median(fms)
+                row["fused_backward_in_forwards"] = (row["fused_step_ms_median"] - row["fused_forward_ms_median"]) \
+                    / row["fused_forward_ms_median"]
+        row["fused_speedup_over_composite"] = row["composite_step_ms_median"] / row["fused_step_ms_median"]
+        rows.append(row)
+        print(f"[cnf train] B={B}: fused step {row['fused_step_ms_median']:.2f} ms (forward alone "
+              f"{row['fused_forward_ms_median']:.2f} ms), composite step {row['composite_step_ms_median']:.1f} ms; "
+              f"fused is {row['fused_speedup_over_composite']:.1f}x", file=sys.stderr, flush=True)
+    res = {"model": f"ContinuousFlow({d}, {H})", "device": torch.cuda.get_device_name(0), "workload": "NLL step",
+           "replays": a.replays, "composite_replays": a.eager_replays, "results": rows}
+    line = json.dumps(res)
+    print(line)
+    out = a.out or os.path.join(ROOT, "profiles", "cnf_train.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="4096,1048576")
+    ap.add_argument("--train", action="store_true",
+                    help="time one NLL step, fused backward against the composite recompute, at B = 4096 and "
+                         "65536 (or --batches); writes profiles/cnf_train.json (or --out)")
+    ap.add_argument("--batches", default=None)
     ap.add_argument("--replays", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--eager-replays", type=int, default=3)
@@ -69,6 +134,9 @@ def main():
     ap.add_argument("--hidden", type=int, default=64)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.train:
+        return train(a)
+    a.batches = a.batches or "4096,1048576"
     dev = torch.device("cuda:0")
     d, H = a.dim, a.hidden
     flow = make_flow(d, H, dev)
