@@ -43,34 +43,27 @@ __global__ void affine_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const float
             const NfxMlpRaw& P = net ? b_net : s_net;
             const int o = i - net * L.net;
             if (o < L.b1) {
-                int t = o - L.w1, lane = t & 63, ks = (t >> 6) % L.KS1, ht = (t >> 6) / L.KS1;
-                int row = 32 * ht + (lane & 31), col = 2 * ks + (lane >> 5);
-                v = (row < H && col < d) ? mlp_weight(P, 0, d, row, col) : 0.f;
+                const RowCol e = a1_elem(o - L.w1, L.KS1);
+                v = (e.row < H && e.col < d) ? mlp_weight(P, 0, d, e.row, e.col) : 0.f;
             } else if (o < L.w2) {
-                int t = o - L.b1, r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-                int row = 32 * ht + crow(r, h);
+                int row = acc_vec_row(o - L.b1);
                 v = row < H ? mlp_bias(P, 0, row) : 0.f;
             } else if (o < L.b2) {
-                int t = o - L.w2, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-                int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-                int row = 32 * hto + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+                const ATileElem e = a_tile_elem(o - L.w2);
+                int row = 32 * (e.tile / HT) + e.row, col = 32 * (e.tile % HT) + e.k;
                 v = (row < H && col < H) ? mlp_weight(P, 1, H, row, col) : 0.f;
             } else if (o < L.w3) {
-                int t = o - L.b2, r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-                int row = 32 * ht + crow(r, h);
+                int row = acc_vec_row(o - L.b2);
                 v = row < H ? mlp_bias(P, 1, row) : 0.f;
             } else if (o < L.b3 && d > 8) {  // MFMA A-operand tiles of the output layer
-                int t = o - L.w3, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-                int kt = (t >> 10) % HT, j = (t >> 10) / HT;
-                int row = 32 * j + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+                const ATileElem e = a_tile_elem(o - L.w3);
+                int row = 32 * (e.tile / HT) + e.row, col = 32 * (e.tile % HT) + e.k;
                 v = (row < d && col < H) ? mlp_weight(P, 2, H, row, col) : 0.f;
             } else if (o < L.b3) {
-                int t = o - L.w3, r = t & 15, h = (t >> 4) & 1, ht = (t >> 5) % HT, j = (t >> 5) / HT;
-                int col = 32 * ht + crow(r, h);
+                int t = o - L.w3, j = t / (32 * HT), col = acc_vec_row(t % (32 * HT));
                 v = col < H ? mlp_weight(P, 2, H, j, col) : 0.f;
             } else if (d > 8) {  // output bias in accumulator order
-                int t = o - L.b3, r = t & 15, h = (t >> 4) & 1, j = t >> 5;
-                int row = 32 * j + crow(r, h);
+                int row = acc_vec_row(o - L.b3);
                 v = row < d ? mlp_bias(P, 2, row) : 0.f;
             } else {
                 int j = o - L.b3;

@@ -154,7 +154,7 @@ __device__ __forceinline__ void affine_net(const float* __restrict__ P, const Af
             for (int rq = 0; rq < 4; ++rq) {
                 // (a one-group-ahead weight prefetch here measured 5% slower: the compiler
                 // then interleaves both nets at 217 VGPRs = 2 waves/SIMD instead of 3)
-                const f32x4 w = wg[((hto * HT + kt) * 4 + rq) * 64];
+                const f32x4 w = wg[a_quad(a_tile(hto, kt, HT), rq) * 64];
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     a0 = mfma32(w[rr], h1[kt][0][4 * rq + rr], a0);
@@ -761,7 +761,7 @@ __device__ __forceinline__ void wide_net(const float* __restrict__ P, const Affi
         for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w2 + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w2 + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], h1[kt][4 * rq + rr], a);
             }
@@ -778,7 +778,7 @@ __device__ __forceinline__ void wide_net(const float* __restrict__ P, const Affi
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w3 + (((j * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w3 + (a_quad(a_tile(j, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], h2[kt][4 * rq + rr], a);
                 }

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(128 * HT) void affine_small_kernel(
 #pragma unroll
         for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
-            for (int rq = 0; rq < 4; ++rq) w2r[kt][rq] = wg[((hto * HT + kt) * 4 + rq) * 64];
+            for (int rq = 0; rq < 4; ++rq) w2r[kt][rq] = wg[a_quad(a_tile(hto, kt, HT), rq) * 64];
     }
     __syncthreads();
     const float* sb1 = sw + net * NPN;

@@ -71,12 +71,12 @@ __global__ void affine_train_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const
             const NfxMlpRaw& P = net ? b_net : s_net;
             const int o = i - net * L.net;
             if (o < L.c1) {  // w1 [HT][KS1][64]
-                const int t = o - L.w1, lane = t & 63, ks = (t >> 6) % L.KS1, ht = (t >> 6) / L.KS1;
-                const int row = 32 * ht + (lane & 31), c = 2 * ks + (lane >> 5);
+                const RowCol e = a1_elem(o - L.w1, L.KS1);
+                const int row = e.row, c = e.col;
                 if (row < H && c < d) v = (float)(bn_fold(stats1, Hp, net, row, eps).r * (double)raw_w(P, 0, d, row, c));
             } else if (o < L.w2) {  // c1, g1, e1 [HT][32] accumulator order
                 const int which = (o - L.c1) / (HT * 32), t = (o - L.c1) % (HT * 32);
-                const int row = 32 * (t >> 5) + crow(t & 15, (t >> 4) & 1);
+                const int row = acc_vec_row(t);
                 if (row < H) {
                     if (which == 0) {
                         const BnFold f = bn_fold(stats1, Hp, net, row, eps);
@@ -86,13 +86,12 @@ __global__ void affine_train_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const
                     }
                 }
             } else if (o < L.c2) {  // w2 [o][kt][rq][lane][rr]
-                const int t = o - L.w2, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-                const int kt = (t >> 10) % HT, ot = (t >> 10) / HT;
-                const int row = 32 * ot + (lane & 31), c = 32 * kt + crow(4 * rq + rr, lane >> 5);
+                const ATileElem e = a_tile_elem(o - L.w2);
+                const int row = 32 * (e.tile / HT) + e.row, c = 32 * (e.tile % HT) + e.k;
                 if (row < H && c < H) v = (float)(bn_fold(stats2, Hp, net, row, eps).r * (double)raw_w(P, 1, H, row, c));
             } else if (o < L.w3) {  // c2, g2, e2
                 const int which = (o - L.c2) / (HT * 32), t = (o - L.c2) % (HT * 32);
-                const int row = 32 * (t >> 5) + crow(t & 15, (t >> 4) & 1);
+                const int row = acc_vec_row(t);
                 if (row < H) {
                     if (which == 0) {
                         const BnFold f = bn_fold(stats2, Hp, net, row, eps);
@@ -103,23 +102,22 @@ __global__ void affine_train_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const
                 }
             } else if (o < L.b3) {  // w3 [D][HT][32]
                 const int t = o - L.w3, j = t / (HT * 32), a = t % (HT * 32);
-                const int c = 32 * (a >> 5) + crow(a & 15, (a >> 4) & 1);
+                const int c = acc_vec_row(a);
                 if (j < d && c < H) v = raw_w(P, 2, H, j, c);
             } else if (o < L.w2t) {
                 const int j = o - L.b3;
                 if (j < d) v = raw_b(P, 2, j);
             } else if (o < L.w1c) {  // w2t [kt][o][rq][lane][rr]: A[i][k] = W2r[32 o + k][32 kt + i]
-                const int t = o - L.w2t, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-                const int ot = (t >> 10) % HT, kt = (t >> 10) / HT;
-                const int row = 32 * ot + crow(4 * rq + rr, lane >> 5), c = 32 * kt + (lane & 31);
+                const ATileElem e = a_tile_elem(o - L.w2t);
+                const int row = 32 * (e.tile % HT) + e.k, c = 32 * (e.tile / HT) + e.row;
                 if (row < H && c < H) v = (float)(bn_fold(stats2, Hp, net, row, eps).r * (double)raw_w(P, 1, H, row, c));
             } else if (o < L.m2) {  // w1c [D][HT][32]: (diag(r1) W1)[row][j]
                 const int t = o - L.w1c, j = t / (HT * 32), a = t % (HT * 32);
-                const int row = 32 * (a >> 5) + crow(a & 15, (a >> 4) & 1);
+                const int row = acc_vec_row(a);
                 if (j < d && row < H) v = (float)(bn_fold(stats1, Hp, net, row, eps).r * (double)raw_w(P, 0, d, row, j));
             } else {  // m2, r2 [HT][32]: BN2 mean and 1/sqrt(var + eps), accumulator order
                 const int which = (o - L.m2) / (HT * 32), t = (o - L.m2) % (HT * 32);
-                const int row = 32 * (t >> 5) + crow(t & 15, (t >> 4) & 1);
+                const int row = acc_vec_row(t);
                 if (row < H) {
                     const BnFold f = bn_fold(stats2, Hp, net, row, eps);
                     v = (float)(which == 0 ? f.mean : f.r);
@@ -151,25 +149,20 @@ __global__ void affine_train_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const
                 return (float)(a * ((double)raw_b(P, layer, row) - f.mean) + (double)raw_be(P, layer, row));
             };
             if (o < E.b1) {
-                const int t = o - E.w1, lane = t & 63, ks = (t >> 6) % E.KS1, ht = (t >> 6) / E.KS1;
-                const int row = 32 * ht + (lane & 31), c = 2 * ks + (lane >> 5);
-                if (row < H && c < d) v = wfold(0, d, stats1, row, c);
+                const RowCol e = a1_elem(o - E.w1, E.KS1);
+                if (e.row < H && e.col < d) v = wfold(0, d, stats1, e.row, e.col);
             } else if (o < E.w2) {
-                const int t = o - E.b1, r = t & 15, hh = (t >> 4) & 1, ht = t >> 5;
-                const int row = 32 * ht + crow(r, hh);
+                const int row = acc_vec_row(o - E.b1);
                 if (row < H) v = bfold(0, stats1, row);
             } else if (o < E.b2) {
-                const int t = o - E.w2, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-                const int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-                const int row = 32 * hto + (lane & 31), c = 32 * kt + crow(4 * rq + rr, lane >> 5);
+                const ATileElem e = a_tile_elem(o - E.w2);
+                const int row = 32 * (e.tile / HT) + e.row, c = 32 * (e.tile % HT) + e.k;
                 if (row < H && c < H) v = wfold(1, H, stats2, row, c);
             } else if (o < E.w3) {
-                const int t = o - E.b2, r = t & 15, hh = (t >> 4) & 1, ht = t >> 5;
-                const int row = 32 * ht + crow(r, hh);
+                const int row = acc_vec_row(o - E.b2);
                 if (row < H) v = bfold(1, stats2, row);
             } else if (o < E.b3) {
-                const int t = o - E.w3, r = t & 15, hh = (t >> 4) & 1, ht = (t >> 5) % HT, j = (t >> 5) / HT;
-                const int c = 32 * ht + crow(r, hh);
+                const int t = o - E.w3, j = t / (32 * HT), c = acc_vec_row(t % (32 * HT));
                 if (c < H) v = raw_w(P, 2, H, j, c);
             } else {
                 const int j = o - E.b3;

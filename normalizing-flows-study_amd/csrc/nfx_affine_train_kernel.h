@@ -3,7 +3,7 @@
 //
 // Every kernel here walks the batch in 32-sample tiles, one tile per wave per iteration
 // (grid-stride), with the conditioner MLPs on fp32 MFMA exactly like the eval kernel: hidden
-// activations in accumulator layout, "hidden-unit rows x sample columns" (nfx_common.h).
+// activations in accumulator layout, "hidden-unit rows x sample columns" (nfx_tile.h).
 // Reductions over the SAMPLE dimension (BatchNorm statistics, weight and BN-parameter
 // gradients) need the sample index off the lane: a per-wave LDS transpose turns an
 // accumulator tile into lane l <-> feature (l & 31), samples 16*(l >> 5) + t (t = 0..15).
@@ -389,7 +389,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(train_waves
                 for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 w = wg[((o * HT + kt) * 4 + rq) * 64];
+                        const f32x4 w = wg[a_quad(a_tile(o, kt, HT), rq) * 64];
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], act[kt][4 * rq + rr], a);
                     }
@@ -449,7 +449,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(train_waves
                 for (int o = 0; o < HT; ++o)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 w = wt[((kt * HT + o) * 4 + rq) * 64];
+                        const f32x4 w = wt[a_quad(a_tile(kt, o, HT), rq) * 64];
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) ga = mfma32(w[rr], e2t[o][4 * rq + rr], ga);
                     }

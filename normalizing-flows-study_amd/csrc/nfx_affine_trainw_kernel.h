@@ -274,7 +274,7 @@ __global__ __launch_bounds__(kTWGroups * 4 * 64) void affine_trainw_kernel(
                 for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 w = wg[((o * HT + kt) * 4 + rq) * 64];
+                        const f32x4 w = wg[a_quad(a_tile(o, kt, HT), rq) * 64];
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], a1[kt][4 * rq + rr], a);
                     }
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(kTWGroups * 4 * 64) void affine_trainw_kernel(
                     for (int op = 0; op < HT; ++op) {
                         f32x4 w[4];
 #pragma unroll
-                        for (int rq = 0; rq < 4; ++rq) w[rq] = wt[((o * HT + op) * 4 + rq) * 64];
+                        for (int rq = 0; rq < 4; ++rq) w[rq] = wt[a_quad(a_tile(o, op, HT), rq) * 64];
 #pragma unroll
                         for (int rq = 0; rq < 4; ++rq)
 #pragma unroll

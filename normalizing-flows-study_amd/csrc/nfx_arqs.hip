@@ -30,31 +30,25 @@ __global__ void arqs_pack_kernel(NfxMlpRaw net, int d, int H, int K, float* pack
         if (o < L.b1) {  // w2 / w3 A operands
             const int layer = o < L.w3 ? 1 : 2;
             const int t = o - (layer == 1 ? L.w2 : L.w3);
-            const int rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            const int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-            const int row = 32 * hto + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(t);
+            const int row = 32 * (e.tile / HT) + e.row, col = 32 * (e.tile % HT) + e.k;
             v = (row < H && col < H) ? mlp_weight(net, layer, H, row, col) : 0.f;
         } else if (o < L.w1t) {  // b1 b2 b3
             const int layer = (o - L.b1) / (HT * 32);
             const int t = (o - L.b1) % (HT * 32);
-            const int r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-            const int row = 32 * ht + crow(r, h);
+            const int row = acc_vec_row(t);
             v = row < H ? mlp_bias(net, layer, row) : 0.f;
         } else if (o < L.w4) {  // w1t
             const int t = o - L.w1t;
-            const int r = t & 15, h = (t >> 4) & 1, ht = (t >> 5) % HT, j = (t >> 5) / HT;
-            const int row = 32 * ht + crow(r, h);
+            const int j = t / (32 * HT), row = acc_vec_row(t % (32 * HT));
             v = row < H ? mlp_weight(net, 0, d, row, j) : 0.f;
         } else if (o < L.b4) {  // w4: the R rows of step i
-            const int t = o - L.w4;
-            const int rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            const int kt = (t >> 10) % HT, i = (t >> 10) / HT;
-            const int m = lane & 31, col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(o - L.w4);
+            const int i = e.tile / HT, m = e.row, col = 32 * (e.tile % HT) + e.k;
             v = (m < R && col < H) ? mlp_weight(net, 3, H, i * R + m, col) : 0.f;
         } else {  // b4
             const int t = o - L.b4;
-            const int r = t & 15, h = (t >> 4) & 1, i = t >> 5;
-            const int m = crow(r, h);
+            const int i = t >> 5, m = acc_vec_row(t & 31);
             v = m < R ? mlp_bias(net, 3, i * R + m) : 0.f;
         }
         packed[o] = v;

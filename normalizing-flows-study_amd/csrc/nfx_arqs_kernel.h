@@ -77,8 +77,8 @@ __global__ __launch_bounds__(64 * HT) void arqs_kernel(ArqsArgs A) {
         for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
-                w2r[kt][rq] = g2[((w * HT + kt) * 4 + rq) * 64];
-                w3r[kt][rq] = g3[((w * HT + kt) * 4 + rq) * 64];
+                w2r[kt][rq] = g2[a_quad(a_tile(w, kt, HT), rq) * 64];
+                w3r[kt][rq] = g3[a_quad(a_tile(w, kt, HT), rq) * 64];
             }
     }
     const f32x16 b2v = load_bias16(P + L.b2 + w * 32, h);
@@ -97,7 +97,7 @@ __global__ __launch_bounds__(64 * HT) void arqs_kernel(ArqsArgs A) {
             {
                 const f32x4* g4 = reinterpret_cast<const f32x4*>(P + L.w4) + lane;
 #pragma unroll
-                for (int rq = 0; rq < 4; ++rq) w4r[rq] = g4[((i * HT + w) * 4 + rq) * 64];
+                for (int rq = 0; rq < 4; ++rq) w4r[rq] = g4[a_quad(a_tile(i, w, HT), rq) * 64];
             }
             const float xin = own ? A.in[s * A.d + i] : 0.f;
             // layer 2 (own tile)

@@ -57,28 +57,23 @@ __global__ void cnf_pack_kernel(const float* __restrict__ w1, const float* __res
     for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < L.total; o += gridDim.x * blockDim.x) {
         float v = 0.f;
         if (o < L.b1) {  // w1: layer-1 A operand over [z; t]
-            const int t = o - L.w1;
-            const int lane = t & 63, ks = (t >> 6) % L.KS1, ht = (t >> 6) / L.KS1;
-            const int row = 32 * ht + (lane & 31), k = 2 * ks + (lane >> 5);
-            v = k <= d ? w1[row * (d + 1) + k] : 0.f;
+            const RowCol e = a1_elem(o - L.w1, L.KS1);
+            v = e.col <= d ? w1[e.row * (d + 1) + e.col] : 0.f;
         } else if (o < L.w3) {  // b1, b2
             const bool second = o >= L.b2;
             const int t = o - (second ? L.b2 : L.b1);
-            const int row = 32 * (t >> 5) + crow(t & 15, (t >> 4) & 1);
+            const int row = acc_vec_row(t);
             v = second ? b2[row] : b1[row];
         } else if (o < L.b3) {  // w3: row j of W3
-            const int t = o - L.w3;
-            const int ht = (t >> 5) % HT, j = (t >> 5) / HT;
-            v = w3[j * H + 32 * ht + crow(t & 15, (t >> 4) & 1)];
+            const int t = o - L.w3, j = t / H;
+            v = w3[j * H + acc_vec_row(t % H)];
         } else if (o < L.c2) {  // b3
             const int j = o - L.b3;
             v = j < d ? b3[j] : 0.f;
         } else {  // c2, w2: A operands over (out row k, hidden input j)
             const bool trace = o < L.w2;
-            const int t = o - (trace ? L.c2 : L.w2);
-            const int rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            const int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-            const int k = 32 * hto + (lane & 31), j = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(o - (trace ? L.c2 : L.w2));
+            const int k = 32 * (e.tile / HT) + e.row, j = 32 * (e.tile % HT) + e.k;
             v = w2[k * H + j];
             if (trace) {  // C[k, j] = W2[k, j] * sum_i W3[i, k] W1[j, i]
                 double n = 0.0;

@@ -63,10 +63,8 @@ __global__ void cnf_bwd_pack_kernel(const float* __restrict__ w1, const float* _
         float v = 0.f;
         if (o < L.w1c) {  // c2t, w2t: A operands over (out row j, contraction index k) of M^T
             const bool trace = o < L.w2t;
-            const int t = o - (trace ? L.c2t : L.w2t);
-            const int rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            const int kt = (t >> 10) % HT, jo = (t >> 10) / HT;
-            const int j = 32 * jo + (lane & 31), k = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(o - (trace ? L.c2t : L.w2t));
+            const int j = 32 * (e.tile / HT) + e.row, k = 32 * (e.tile % HT) + e.k;
             v = w2[k * H + j];
             if (trace) {  // C[k, j], rounded as the forward pack rounds it
                 double n = 0.0;
@@ -74,9 +72,8 @@ __global__ void cnf_bwd_pack_kernel(const float* __restrict__ w1, const float* _
                 v = (float)((double)v * n);
             }
         } else if (o < L.w1c + d * HT * 32) {  // w1c: column i of W1
-            const int t = o - L.w1c;
-            const int ht = (t >> 5) % HT, i = (t >> 5) / HT;
-            v = w1[(32 * ht + crow(t & 15, (t >> 4) & 1)) * (d + 1) + i];
+            const int t = o - L.w1c, i = t / H;
+            v = w1[acc_vec_row(t % H) * (d + 1) + i];
         }
         packed[o] = v;
     }
@@ -91,12 +88,6 @@ __global__ void cnf_bwd_reduce_kernel(const float* __restrict__ ws, int nslots, 
     tot[e] = acc;
 }
 
-// Register r and lane half of row `row` (0..31) of an accumulator tile: the inverse of crow.
-__device__ __forceinline__ int acc_index(int row, int colv) {
-    const int hh = (row >> 2) & 1, r = (row & 3) + 4 * (row >> 3);
-    return r * 64 + hh * 32 + colv;
-}
-
 // One thread per gradient element: decode the register order, apply the finish step.
 __global__ void cnf_bwd_finish_kernel(const double* __restrict__ tot, const float* __restrict__ w1,
                                       const float* __restrict__ w2, const float* __restrict__ w3, int d, int H,
@@ -107,7 +98,7 @@ __global__ void cnf_bwd_finish_kernel(const double* __restrict__ tot, const floa
     const int nW2 = H * H, nW1 = H * (d + 1), nW3 = d * H;
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     auto tile_hh = [&](int base, int k, int j) -> double {  // element (k, j) of a dumped H x H sum
-        return tot[base + ((k >> 5) * HT + (j >> 5)) * 1024 + acc_index(k & 31, j & 31)];
+        return tot[base + ((k >> 5) * HT + (j >> 5)) * 1024 + acc_dump_index(k & 31, j & 31)];
     };
     auto nb = [&](int k, int j) -> double { return tile_hh(P.c, k, j) * (double)w2[k * H + j]; };
     if (e < nW2) {
@@ -117,13 +108,13 @@ __global__ void cnf_bwd_finish_kernel(const double* __restrict__ tot, const floa
         gw2[e] = (float)(tile_hh(P.w2, k, j) + tile_hh(P.c, k, j) * n);
     } else if (e < nW2 + nW1) {
         const int j = (e - nW2) / (d + 1), i = (e - nW2) % (d + 1);
-        double g = tot[P.g1 + (j >> 5) * 1024 + acc_index(j & 31, i)];
+        double g = tot[P.g1 + (j >> 5) * 1024 + acc_dump_index(j & 31, i)];
         if (i < d)
             for (int k = 0; k < H; ++k) g += nb(k, j) * (double)w3[i * H + k];
         gw1[e - nW2] = (float)g;
     } else if (e < nW2 + nW1 + nW3) {
         const int i = (e - nW2 - nW1) / H, k = (e - nW2 - nW1) % H;
-        double g = tot[P.g3 + (k >> 5) * 1024 + acc_index(k & 31, i)];
+        double g = tot[P.g3 + (k >> 5) * 1024 + acc_dump_index(k & 31, i)];
         for (int j = 0; j < H; ++j) g += nb(k, j) * (double)w1[j * (d + 1) + i];
         gw3[e - nW2 - nW1] = (float)g;
     } else if (e < nW2 + nW1 + nW3 + 2 * H) {

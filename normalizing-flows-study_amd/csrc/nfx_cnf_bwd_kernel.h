@@ -193,8 +193,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 w = w2l[((hto * HT + kt) * 4 + rq) * 64];
-                    const f32x4 cw = c2l[((hto * HT + kt) * 4 + rq) * 64];
+                    const f32x4 w = w2l[a_quad(a_tile(hto, kt, HT), rq) * 64];
+                    const f32x4 cw = c2l[a_quad(a_tile(hto, kt, HT), rq) * 64];
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         const float hv = h1[kt][4 * rq + rr];
@@ -307,8 +307,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 w = w2tl[((jo * HT + kt) * 4 + rq) * 64];
-                    const f32x4 cw = c2tl[((jo * HT + kt) * 4 + rq) * 64];
+                    const f32x4 w = w2tl[a_quad(a_tile(jo, kt, HT), rq) * 64];
+                    const f32x4 cw = c2tl[a_quad(a_tile(jo, kt, HT), rq) * 64];
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         m = mfma32(w[rr], a2[kt][4 * rq + rr], m);

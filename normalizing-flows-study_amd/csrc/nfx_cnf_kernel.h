@@ -150,7 +150,7 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
         for (int hto = 0; hto < HT; ++hto) {
             auto w2 = [&](int kt, int rq) -> f32x4 {
                 if constexpr (W2REG) return w2r[(hto * HT + kt) * 4 + rq];
-                else return w2l[((hto * HT + kt) * 4 + rq) * 64];
+                else return w2l[a_quad(a_tile(hto, kt, HT), rq) * 64];
             };
             // h2 tile hto, and beside it the same tile of C g1 (g1 = 1 - h1^2): two independent chains
             f32x16 a = load_bias16(s + L.b2 + hto * 32, h);
@@ -160,7 +160,7 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const f32x4 w = w2(kt, rq);
-                    const f32x4 cw = c2l[((hto * HT + kt) * 4 + rq) * 64];
+                    const f32x4 cw = c2l[a_quad(a_tile(hto, kt, HT), rq) * 64];
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         const float hv = h1[kt][4 * rq + rr];

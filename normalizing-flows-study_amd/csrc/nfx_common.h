@@ -1,15 +1,8 @@
 // Shared device helpers for the gfx950 flow kernels.
 //
-// MFMA tile convention used by every conditioner MLP in this library
-// (v_mfma_f32_32x32x2_f32, exact fp32, 64 FLOP/clk/SIMD):
-//   D[32 x 32] += A[32 x 2] * B[2 x 32]
-//   A: lane l holds A[i = l & 31][k = l >> 5]       (weights, packed on device by *_pack)
-//   B: lane l holds B[k = l >> 5][j = l & 31]       (activations, column j = one sample)
-//   C/D: lane l, register r holds D[crow(r, l >> 5)][l & 31]
-// Activations therefore live "hidden-unit rows x sample columns": a layer's accumulator tile
-// is directly the B operand of the next layer (k-step (kt, r) reads register r of tile kt),
-// with the weight operand permuted on the host side of the pack to match. No LDS round trip
-// and no lane shuffles between layers.
+// The MFMA tile convention of every conditioner MLP in this library (operand and accumulator
+// lane order, the packed weight tile, accumulator-order vectors, dumped tiles) is defined once,
+// as functions, in nfx_tile.h. Packs and kernels call those; none restates the arithmetic.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,15 +10,13 @@
 
 #include "../../include/nfx.h"
 #include "nfx_pick.h"
+#include "nfx_tile.h"
 
 namespace nfx {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// Row of register r in lane-half h of a 32x32 fp32 MFMA accumulator.
-__host__ __device__ constexpr int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);

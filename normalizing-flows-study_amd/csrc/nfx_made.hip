@@ -22,27 +22,25 @@ __global__ void made_pack_kernel(NfxMlpRaw net, int d, int H, float* packed) {
             int row = 32 * ht + (lane & 31), col = 2 * (4 * g + rr) + (lane >> 5);
             v = (row < H && col < d) ? mlp_weight(net, 0, d, row, col) : 0.f;
         } else if (i < L.w2) {
-            int t = i - L.b1, r = t & 15, h = (t >> 4) & 1, ht = t >> 5, row = 32 * ht + crow(r, h);
+            int row = acc_vec_row(i - L.b1);
             v = row < H ? mlp_bias(net, 0, row) : 0.f;
         } else if (i < L.b2 || (i >= L.w3 && i < L.b3)) {
             const int layer = i < L.b2 ? 1 : 2;
-            int t = i - (layer == 1 ? L.w2 : L.w3), rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-            int row = 32 * hto + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(i - (layer == 1 ? L.w2 : L.w3));
+            int row = 32 * (e.tile / HT) + e.row, col = 32 * (e.tile % HT) + e.k;
             v = (row < H && col < H) ? mlp_weight(net, layer, H, row, col) : 0.f;
         } else if (i < L.w3 || (i >= L.b3 && i < L.w4)) {
             const int layer = i < L.w3 ? 1 : 2;
-            int t = i - (layer == 1 ? L.b2 : L.b3), r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-            int row = 32 * ht + crow(r, h);
+            int row = acc_vec_row(i - (layer == 1 ? L.b2 : L.b3));
             v = row < H ? mlp_bias(net, layer, row) : 0.f;
         } else if (i < L.b4) {
-            int t = i - L.w4, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int kt = (t >> 10) % HT, jw = (t >> 10) / HT, which = jw & 1, j = jw >> 1;
-            int orow = 32 * j + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(i - L.w4);  // tiles [j][mu | alpha][kt]
+            int jw = e.tile / HT, which = jw & 1, j = jw >> 1;
+            int orow = 32 * j + e.row, col = 32 * (e.tile % HT) + e.k;
             v = (orow < d && col < H) ? mlp_weight(net, 3, H, which * d + orow, col) : 0.f;
         } else if (i < L.par_total) {
-            int t = i - L.b4, r = t & 15, h = (t >> 4) & 1, jw = t >> 5, which = jw & 1, j = jw >> 1;
-            int orow = 32 * j + crow(r, h);
+            int t = i - L.b4, jw = t >> 5, which = jw & 1, j = jw >> 1;
+            int orow = 32 * j + acc_vec_row(t & 31);
             v = orow < d ? mlp_bias(net, 3, which * d + orow) : 0.f;
         } else if (i < L.s_b1) {
             int t = i - L.s_w1t, ii = t / Hp, a = t % Hp;

@@ -62,7 +62,7 @@ __device__ __forceinline__ void big_put(float* act, f32x16 (&a)[HT]) {
     for (int t = 0; t < HT; ++t)
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq)
-            *reinterpret_cast<f32x4*>(act + ((t * 4 + rq) * 64 + lane) * 4) =
+            *reinterpret_cast<f32x4*>(act + (a_quad(t, rq) * 64 + lane) * 4) =
                 f32x4{trelu(a[t][4 * rq]), trelu(a[t][4 * rq + 1]), trelu(a[t][4 * rq + 2]), trelu(a[t][4 * rq + 3])};
 }
 
@@ -77,10 +77,10 @@ __device__ __forceinline__ void big_layer(const float* __restrict__ W, int woff,
     for (int kt = 0; kt < HT; ++kt) {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 bv = *reinterpret_cast<const f32x4*>(act + ((kt * 4 + rq) * 64 + lane) * 4);
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(act + (a_quad(kt, rq) * 64 + lane) * 4);
 #pragma unroll
             for (int t = 0; t < HT; ++t) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (((t * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (a_quad(a_tile(t, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) a[t] = mfma32(w[rr], bv[rr], a[t]);
             }
@@ -141,11 +141,11 @@ __global__ __launch_bounds__(kBigWaves * 64) void made_big_par_kernel(
             for (int kt = 0; kt < HT; ++kt) {
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 bv = *reinterpret_cast<const f32x4*>(act + ((kt * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(act + (a_quad(kt, rq) * 64 + lane) * 4);
                     const f32x4 wm = *reinterpret_cast<const f32x4*>(
-                        W + L.w4 + ((((j * 2 + 0) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        W + L.w4 + (a_quad(a_tile(j * 2 + 0, kt, HT), rq) * 64 + lane) * 4);
                     const f32x4 wa = *reinterpret_cast<const f32x4*>(
-                        W + L.w4 + ((((j * 2 + 1) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        W + L.w4 + (a_quad(a_tile(j * 2 + 1, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         mu = mfma32(wm[rr], bv[rr], mu);

@@ -44,10 +44,10 @@ __global__ void made_bwd_pack_kernel(NfxMlpRaw net, int d, int H, float* packed)
         else if (i < L.t2) { base = L.t3; nk = HT; }
         else if (i < L.t1) { base = L.t2; nk = HT; }
         else { base = L.t1; nk = HT; }
-        const int t = i - base, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-        const int kt = (t >> 10) % nk, ot = (t >> 10) / nk;
-        const int row = 32 * ot + (lane & 31);                     // out index (rows of the transposed)
-        const int kk = crow(4 * rq + rr, lane >> 5);               // k index inside the k tile
+        const ATileElem e = a_tile_elem(i - base);
+        const int kt = e.tile % nk, ot = e.tile / nk;
+        const int row = 32 * ot + e.row;                           // out index (rows of the transposed)
+        const int kk = e.k;                                        // k index inside the k tile
         if (i < L.t3) {
             const int j = kt >> 1, which = kt & 1, o = 32 * j + kk;  // output block (mu | alpha)
             v = (row < H && o < d) ? mlp_weight(net, 3, H, which * d + o, row) : 0.f;
@@ -75,7 +75,7 @@ __device__ __forceinline__ void store_fm(float* __restrict__ dst, const f32x16& 
     const int vo = base + col < B ? (int)((col + 4 * h * P) * 4) : (int)0xFFFFFFF0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int rowu = row0 + (r & 3) + 8 * (r >> 2);
+        const int rowu = row0 + crow(r, 0);
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(t[r]), rs, vo, (int)(rowu * P * 4), 0);
     }
 }
@@ -102,7 +102,7 @@ __device__ __forceinline__ f32x16 chain_gmem(const float* __restrict__ A, int ot
     for (int kt = 0; kt < NK; ++kt) {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(A + (((ot * nk_total + kt) * 4 + rq) * 64 + lane) * 4);
+            const f32x4 w = *reinterpret_cast<const f32x4*>(A + (a_quad(a_tile(ot, kt, nk_total), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) acc = mfma32(w[rr], bt[kt][4 * rq + rr], acc);
         }
@@ -121,7 +121,7 @@ __device__ __forceinline__ f32x16 chain_gmem_k(const float* __restrict__ A, int 
     for (int kt = K0; kt < NK; ++kt) {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(A + (((ot * nk_total + kt) * 4 + rq) * 64 + lane) * 4);
+            const f32x4 w = *reinterpret_cast<const f32x4*>(A + (a_quad(a_tile(ot, kt, nk_total), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) acc = mfma32(w[rr], bt[kt][4 * rq + rr], acc);
         }
@@ -235,7 +235,7 @@ __device__ __forceinline__ f32x16 tchain_k(const float* wl, int stride, int ot, 
         // the tile's 16 dwords in flight together (counted waits), then the 16 MFMAs
         float a[16];
 #pragma unroll
-        for (int st = 0; st < 16; ++st) a[st] = tp[4 * ((st & 3) + 8 * (st >> 2))];
+        for (int st = 0; st < 16; ++st) a[st] = tp[4 * crow(st, 0)];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int st = 0; st < 16; ++st) acc = mfma32(a[st], bt[kt][st], acc);
@@ -706,7 +706,7 @@ __global__ __launch_bounds__(64 * kBwdwWaves) void made_bwdw_kernel(
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 wa = *reinterpret_cast<const f32x4*>(Wf + L.w4 + ((((j * 2 + 1) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 wa = *reinterpret_cast<const f32x4*>(Wf + L.w4 + (a_quad(a_tile(j * 2 + 1, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) al = mfma32(wa[rr], h3[kt][4 * rq + rr], al);
                 }
@@ -732,8 +732,8 @@ __global__ __launch_bounds__(64 * kBwdwWaves) void made_bwdw_kernel(
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 wm = *reinterpret_cast<const f32x4*>(Wf + L.w4 + ((((j * 2 + 0) * HT + kt) * 4 + rq) * 64 + lane) * 4);
-                    const f32x4 wa = *reinterpret_cast<const f32x4*>(Wf + L.w4 + ((((j * 2 + 1) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 wm = *reinterpret_cast<const f32x4*>(Wf + L.w4 + (a_quad(a_tile(j * 2 + 0, kt, HT), rq) * 64 + lane) * 4);
+                    const f32x4 wa = *reinterpret_cast<const f32x4*>(Wf + L.w4 + (a_quad(a_tile(j * 2 + 1, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         mu = mfma32(wm[rr], h3[kt][4 * rq + rr], mu);
@@ -785,7 +785,7 @@ __global__ __launch_bounds__(64 * kBwdwWaves) void made_bwdw_kernel(
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
                         const f32x4 w = *reinterpret_cast<const f32x4*>(
-                            Wf + L.t4 + (((ot * 2 * NJ + 2 * j + which) * 4 + rq) * 64 + lane) * 4);
+                            Wf + L.t4 + (a_quad(a_tile(ot, 2 * j + which, 2 * NJ), rq) * 64 + lane) * 4);
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) g3[ot] = mfma32(w[rr], dl[4 * rq + rr], g3[ot]);
                     }

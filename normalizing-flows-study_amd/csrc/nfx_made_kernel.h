@@ -210,7 +210,7 @@ __device__ __forceinline__ void made_hidden(const float* __restrict__ W, int wof
         for (int kt = 0; kt < HT; ++kt) {
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
-                const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     a0 = mfma32(w[rr], hin[kt][0][4 * rq + rr], a0);
@@ -306,9 +306,9 @@ __global__ __launch_bounds__(WLDS ? 512 : 256) void made_parallel_kernel(
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const f32x4 wm = *reinterpret_cast<const f32x4*>(
-                        W + L.w4 + ((((j * 2 + 0) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        W + L.w4 + (a_quad(a_tile(j * 2 + 0, kt, HT), rq) * 64 + lane) * 4);
                     const f32x4 wa = *reinterpret_cast<const f32x4*>(
-                        W + L.w4 + ((((j * 2 + 1) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        W + L.w4 + (a_quad(a_tile(j * 2 + 1, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         const float b0 = h1[kt][0][4 * rq + rr], b1 = h1[kt][1][4 * rq + rr];
@@ -507,7 +507,7 @@ __device__ __forceinline__ void made_hidden1(const float* __restrict__ W, int wo
             f32x4 w[HT];
 #pragma unroll
             for (int hto = 0; hto < HT; ++hto)
-                w[hto] = *reinterpret_cast<const f32x4*>(W + woff + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                w[hto] = *reinterpret_cast<const f32x4*>(W + woff + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
 #pragma unroll
@@ -534,7 +534,7 @@ __device__ __forceinline__ f32x16 hidden_tile(const float* __restrict__ W, int w
     for (int kt = 0; kt < NK; ++kt) {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+            const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], hin[kt][4 * rq + rr], a);
         }
@@ -581,9 +581,9 @@ __device__ __forceinline__ void out_pair(const float* __restrict__ W, const Made
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
             const f32x4 wm = *reinterpret_cast<const f32x4*>(
-                W + L.w4 + ((((j * 2 + 0) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                W + L.w4 + (a_quad(a_tile(j * 2 + 0, kt, HT), rq) * 64 + lane) * 4);
             const f32x4 wa = *reinterpret_cast<const f32x4*>(
-                W + L.w4 + ((((j * 2 + 1) * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                W + L.w4 + (a_quad(a_tile(j * 2 + 1, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 mu = mfma32(wm[rr], hin[kt][4 * rq + rr], mu);

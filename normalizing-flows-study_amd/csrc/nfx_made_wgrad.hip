@@ -181,10 +181,11 @@ __global__ __launch_bounds__(64 * kWgWaves) void made_wgrad_kernel(WgArgs a, int
 __global__ void made_wgrad_assemble_kernel(WgArgs a, const double* sums) {
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < a.T * 1024 + a.NBT * 32; e += gridDim.x * blockDim.x) {
         if (e < a.T * 1024) {
-            const int t = e >> 10, lane = (e >> 4) & 63, r = e & 15;
+            const int t = e >> 10;
+            const RowCol rc = lane_dump_elem(e & 1023);
             const WgLayer& L = a.l[wg_layer_of(a, t)];
             const int lt = t - L.tile0, tmi = lt / L.tn, tni = lt % L.tn;
-            const int row = 32 * tmi + crow(r, lane >> 5), col = 32 * tni + (lane & 31);
+            const int row = 32 * tmi + rc.row, col = 32 * tni + rc.col;
             if (row < L.M && col < L.N) {
                 const size_t o = (size_t)row * L.N + col;
                 const float g = (float)sums[e];

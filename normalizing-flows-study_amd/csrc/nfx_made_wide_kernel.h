@@ -60,7 +60,7 @@ __device__ __forceinline__ void hidden_tile2(const float* __restrict__ W, int wo
     for (int kt = 0; kt < NK; ++kt) {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+            const f32x4 w = *reinterpret_cast<const f32x4*>(W + woff + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 a0 = mfma32(w[rr], hin[kt][0][4 * rq + rr], a0);

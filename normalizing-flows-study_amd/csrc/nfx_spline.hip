@@ -25,32 +25,26 @@ __global__ void spline_pack_kernel(NfxMlpRaw net, const float* mask, int d, int 
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < L.total; i += gridDim.x * blockDim.x) {
         float v = 0.f;
         if (i < L.b1) {
-            const int KS = spline_ks1(d);
-            int t = i - L.w1, lane = t & 63, ks = (t >> 6) % KS, ht = (t >> 6) / KS;
-            int row = 32 * ht + (lane & 31), col = 2 * ks + (lane >> 5);
-            v = (row < H && col < d) ? mlp_weight(net, 0, d, row, col) : 0.f;
+            const RowCol e = a1_elem(i - L.w1, spline_ks1(d));
+            v = (e.row < H && e.col < d) ? mlp_weight(net, 0, d, e.row, e.col) : 0.f;
         } else if (i < L.w2) {
-            int t = i - L.b1, r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-            int row = 32 * ht + crow(r, h);
+            int row = acc_vec_row(i - L.b1);
             v = row < H ? mlp_bias(net, 0, row) : 0.f;
         } else if (i < L.b2) {
-            int t = i - L.w2, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-            int row = 32 * hto + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(i - L.w2);
+            int row = 32 * (e.tile / HT) + e.row, col = 32 * (e.tile % HT) + e.k;
             v = (row < H && col < H) ? mlp_weight(net, 1, H, row, col) : 0.f;
         } else if (i < L.w3) {
-            int t = i - L.b2, r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-            int row = 32 * ht + crow(r, h);
+            int row = acc_vec_row(i - L.b2);
             v = row < H ? mlp_bias(net, 1, row) : 0.f;
         } else if (i < L.b3) {
-            int t = i - L.w3, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int kt = (t >> 10) % HT, tile = (t >> 10) / HT;
-            int dt = spline_tdim(mask, d, tile), p = lane & 31;
-            int col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(i - L.w3);
+            int dt = spline_tdim(mask, d, e.tile / HT), p = e.row;
+            int col = 32 * (e.tile % HT) + e.k;
             v = (dt >= 0 && p < P && col < H) ? mlp_weight(net, 2, H, dt * P + p, col) : 0.f;
         } else if (i < L.mask) {
-            int t = i - L.b3, r = t & 15, h = (t >> 4) & 1, tile = t >> 5;
-            int dt = spline_tdim(mask, d, tile), p = crow(r, h);
+            int t = i - L.b3, tile = t >> 5;
+            int dt = spline_tdim(mask, d, tile), p = acc_vec_row(t & 31);
             v = (dt >= 0 && p < P) ? mlp_bias(net, 2, dt * P + p) : 0.f;
         } else if (i < L.tdim) {
             int j = i - L.mask;

@@ -30,31 +30,26 @@ __global__ void spline_bwd_pack_kernel(NfxMlpRaw net, const float* mask, int d, 
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < BL.total; i += gridDim.x * blockDim.x) {
         float v = 0.f;
         if (i < L.b1) {
-            int t = i - L.w1, lane = t & 63, ks = (t >> 6) & 3, ht = t >> 8;
-            int row = 32 * ht + (lane & 31), col = 2 * ks + (lane >> 5);
-            v = (row < H && col < d) ? mlp_weight(net, 0, d, row, col) : 0.f;
+            const RowCol e = a1_elem(i - L.w1, 4);
+            v = (e.row < H && e.col < d) ? mlp_weight(net, 0, d, e.row, e.col) : 0.f;
         } else if (i < L.w2) {
-            int t = i - L.b1, r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-            int row = 32 * ht + crow(r, h);
+            int row = acc_vec_row(i - L.b1);
             v = row < H ? mlp_bias(net, 0, row) : 0.f;
         } else if (i < L.b2) {
-            int t = i - L.w2, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int kt = (t >> 10) % HT, hto = (t >> 10) / HT;
-            int row = 32 * hto + (lane & 31), col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(i - L.w2);
+            int row = 32 * (e.tile / HT) + e.row, col = 32 * (e.tile % HT) + e.k;
             v = (row < H && col < H) ? mlp_weight(net, 1, H, row, col) : 0.f;
         } else if (i < L.w3) {
-            int t = i - L.b2, r = t & 15, h = (t >> 4) & 1, ht = t >> 5;
-            int row = 32 * ht + crow(r, h);
+            int row = acc_vec_row(i - L.b2);
             v = row < H ? mlp_bias(net, 1, row) : 0.f;
         } else if (i < L.b3) {
-            int t = i - L.w3, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int kt = (t >> 10) % HT, tile = (t >> 10) / HT;
-            int dt = spline_bwd_tdim(mask, d, tile), p = lane & 31;
-            int col = 32 * kt + crow(4 * rq + rr, lane >> 5);
+            const ATileElem e = a_tile_elem(i - L.w3);
+            int dt = spline_bwd_tdim(mask, d, e.tile / HT), p = e.row;
+            int col = 32 * (e.tile % HT) + e.k;
             v = (dt >= 0 && p < P && col < H) ? mlp_weight(net, 2, H, dt * P + p, col) : 0.f;
         } else if (i < L.mask) {
-            int t = i - L.b3, r = t & 15, h = (t >> 4) & 1, tile = t >> 5;
-            int dt = spline_bwd_tdim(mask, d, tile), p = crow(r, h);
+            int t = i - L.b3, tile = t >> 5;
+            int dt = spline_bwd_tdim(mask, d, tile), p = acc_vec_row(t & 31);
             v = (dt >= 0 && p < P) ? mlp_bias(net, 2, dt * P + p) : 0.f;
         } else if (i < L.tdim) {
             int j = i - L.mask;
@@ -66,19 +61,17 @@ __global__ void spline_bwd_pack_kernel(NfxMlpRaw net, const float* mask, int d, 
             for (int j = 0; j < d; ++j) nt += mask[j] == 0.f ? 1 : 0;
             v = (i == L.meta) ? (float)nt : 0.f;
         } else if (i < BL.w3t) {  // w2t [kt][o][rq][lane][rr]: A[i][k] = W2[32 o + k][32 kt + i]
-            int t = i - BL.w2t, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int ot = (t >> 10) % HT, kt = (t >> 10) / HT;
-            int row = 32 * ot + crow(4 * rq + rr, lane >> 5), col = 32 * kt + (lane & 31);
+            const ATileElem e = a_tile_elem(i - BL.w2t);
+            int row = 32 * (e.tile % HT) + e.k, col = 32 * (e.tile / HT) + e.row;
             v = (row < H && col < H) ? mlp_weight(net, 1, H, row, col) : 0.f;
         } else if (i < BL.w1c) {  // w3t [kt][tile][rq][lane][rr]: A[i][k] = W3[dt P + k][32 kt + i]
-            int t = i - BL.w3t, rr = t & 3, lane = (t >> 2) & 63, rq = (t >> 8) & 3;
-            int tile = (t >> 10) % NTM, kt = (t >> 10) / NTM;
-            int dt = spline_bwd_tdim(mask, d, tile), p = crow(4 * rq + rr, lane >> 5);
-            int col = 32 * kt + (lane & 31);
+            const ATileElem e = a_tile_elem(i - BL.w3t);
+            int dt = spline_bwd_tdim(mask, d, e.tile % NTM), p = e.k;
+            int col = 32 * (e.tile / NTM) + e.row;
             v = (dt >= 0 && p < P && col < H) ? mlp_weight(net, 2, H, dt * P + p, col) : 0.f;
         } else if (i < BL.w1c + 8 * HT * 32) {  // w1c [8][HT][32]: W1[row][j]
             int t = i - BL.w1c, j = t / (HT * 32), a = t % (HT * 32);
-            int row = 32 * (a >> 5) + crow(a & 15, (a >> 4) & 1);
+            int row = acc_vec_row(a);
             v = (j < d && row < H) ? mlp_weight(net, 0, d, row, j) : 0.f;
         }
         packed[i] = v;

@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256) void spline_bwd_kernel(
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w2 + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w2 + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], h1[kt][4 * rq + rr], a);
                 }
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) void spline_bwd_kernel(
                 for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w3 + (((t * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w3 + (a_quad(a_tile(t, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], h2[kt][4 * rq + rr], a);
                     }
@@ -593,7 +593,7 @@ __global__ __launch_bounds__(256) void spline_bwd_kernel(
                 for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 w = wt[((kt * NTMAX + t) * 4 + rq) * 64];
+                        const f32x4 w = wt[a_quad(a_tile(kt, t, NTMAX), rq) * 64];
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) g2[kt] = mfma32(w[rr], e[4 * rq + rr], g2[kt]);
                     }
@@ -651,7 +651,7 @@ __global__ __launch_bounds__(256) void spline_bwd_kernel(
                 for (int o2 = 0; o2 < HT; ++o2)
 #pragma unroll
                     for (int rq = 0; rq < 4; ++rq) {
-                        const f32x4 w = wt[((kt * HT + o2) * 4 + rq) * 64];
+                        const f32x4 w = wt[a_quad(a_tile(kt, o2, HT), rq) * 64];
 #pragma unroll
                         for (int rr = 0; rr < 4; ++rr) g1 = mfma32(w[rr], g2[o2][4 * rq + rr], g1);
                     }

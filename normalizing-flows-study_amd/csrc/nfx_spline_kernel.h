@@ -310,7 +310,7 @@ __device__ __forceinline__ void spline_unit_apply(const float* P, const SplineLa
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
                 const f32x4 w = *reinterpret_cast<const f32x4*>(
-                    P + L.w2 + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    P + L.w2 + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     a0 = mfma32(w[rr], h1[kt][0][4 * rq + rr], a0);
@@ -339,7 +339,7 @@ __device__ __forceinline__ void spline_unit_apply(const float* P, const SplineLa
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
                 const f32x4 w = *reinterpret_cast<const f32x4*>(
-                    P + L.w3 + (((t * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    P + L.w3 + (a_quad(a_tile(t, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     a0 = mfma32(w[rr], h2[kt][0][4 * rq + rr], a0);
@@ -523,7 +523,7 @@ __device__ __forceinline__ void spline_unit_hidden(const float* P, const SplineL
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
                 const f32x4 w = *reinterpret_cast<const f32x4*>(
-                    P + L.w2 + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    P + L.w2 + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                 for (int rr = 0; rr < 4; ++rr) {
                     a0 = mfma32(w[rr], h1[kt][0][4 * rq + rr], a0);
@@ -554,7 +554,7 @@ __device__ __forceinline__ void spline_unit_params(const float* P, const SplineL
     for (int kt = 0; kt < HT; ++kt) {
 #pragma unroll
         for (int rq = 0; rq < 4; ++rq) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w3 + (((t * HT + kt) * 4 + rq) * 64 + lane) * 4);
+            const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w3 + (a_quad(a_tile(t, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
             for (int rr = 0; rr < 4; ++rr) {
                 a0 = mfma32(w[rr], h2[kt][0][4 * rq + rr], a0);
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(256, (DS == 2 && HT <= 2) ? 3 : 1) void spline_coup
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const f32x4 w = *reinterpret_cast<const f32x4*>(
-                        P + L.w2 + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        P + L.w2 + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         a0 = mfma32(w[rr], h1[kt][0][4 * rq + rr], a0);
@@ -761,7 +761,7 @@ __global__ __launch_bounds__(256, (DS == 2 && HT <= 2) ? 3 : 1) void spline_coup
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const f32x4 w = *reinterpret_cast<const f32x4*>(
-                        P + L.w3 + (((t * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                        P + L.w3 + (a_quad(a_tile(t, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
                         a0 = mfma32(w[rr], h2[kt][0][4 * rq + rr], a0);
@@ -917,7 +917,7 @@ __global__ __launch_bounds__(64 * kSplineWideWaves) void spline_wide_kernel(
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w2 + (((hto * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 w = *reinterpret_cast<const f32x4*>(P + L.w2 + (a_quad(a_tile(hto, kt, HT), rq) * 64 + lane) * 4);
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) a = mfma32(w[rr], h1[kt][4 * rq + rr], a);
                 }
@@ -934,9 +934,9 @@ __global__ __launch_bounds__(64 * kSplineWideWaves) void spline_wide_kernel(
             for (int kt = 0; kt < HT; ++kt)
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
-                    const f32x4 w0 = *reinterpret_cast<const f32x4*>(P + L.w3 + (((tt * HT + kt) * 4 + rq) * 64 + lane) * 4);
+                    const f32x4 w0 = *reinterpret_cast<const f32x4*>(P + L.w3 + (a_quad(a_tile(tt, kt, HT), rq) * 64 + lane) * 4);
                     const f32x4 w1 = two ? *reinterpret_cast<const f32x4*>(
-                                               P + L.w3 + ((((tt + 1) * HT + kt) * 4 + rq) * 64 + lane) * 4)
+                                               P + L.w3 + (a_quad(a_tile(tt + 1, kt, HT), rq) * 64 + lane) * 4)
                                          : f32x4{};
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) {
