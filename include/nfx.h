@@ -10,7 +10,23 @@
  * Conventions (all entry points):
  *   - Every tensor pointer is a DEVICE pointer owned by the caller (PyTorch allocator).
  *     The library allocates nothing persistent and frees nothing.
- *   - Tensors are fp32, row-major and contiguous: x/z `[B, d]`, log_det `[B]`.
+ *   - Tensors are fp32, row-major and contiguous: x/z `[B, d]`, log_det `[B]`. A pointer is all
+ *     an entry point receives, so strides do not exist here: the caller passes dense arrays.
+ *   - Every tensor pointer is 16-byte aligned (what an allocator returns; a view that starts at
+ *     an odd float of a larger buffer is not): rows of d = 2 / 4 and the packed images move as
+ *     8- and 16-byte words. The exceptions take any 4-byte-aligned pointer and pick a scalar-load
+ *     variant for an operand off a 16-byte boundary: nfx_linear_forward / _backward_data /
+ *     _backward_weight (x, w, wmask, gy) and nfx_flowbn_apply / _moments / _backward (in, out,
+ *     grad_out, grad_in). Read and written one float at a time, so also free to sit on any
+ *     4-byte boundary: the BatchNorm per-feature vectors (gamma, beta, running_mean,
+ *     running_var) of nfx_bn_prepare, nfx_flowbn_*, nfx_affine_train_update_running* and
+ *     nfx_affine_eval_stats (a module's own buffers, updated in place), and every tensor of
+ *     nfx_rqs_unit / nfx_rqs_unit_backward. Workspaces are 16-byte aligned everywhere.
+ *   - Outputs, workspaces and every buffer an entry point fills (packed images, statistics and
+ *     sum blocks, kept activations, factor rows, the trajectory) may hold anything on entry: each
+ *     word that is read was written by the same call sequence first, nothing is accumulated into
+ *     a buffer the library did not initialise, and no pad is left to chance. The one exception is
+ *     an explicit `accumulate` = 1 argument, which adds into the caller's values.
  *   - `stream` is a hipStream_t (0 = null stream). Every call is stream-ordered and
  *     asynchronous; no call synchronises the device, so calls can be captured in a hipGraph.
  *   - Return 0 on success; < 0 on error, with a message in nfx_last_error() (thread-local).
@@ -305,7 +321,8 @@ int nfx_made_affine_sample(const float* packed, uint64_t seed, uint64_t* rng_sta
  * from grad_out = dL/dz [B, d] and grad_log_det = dL/dlog_det [B]. The parameter gradients
  * are contractions over the sample dimension (nfx_made_backward_weights): dW4 = [δμ;δα]·h3ᵀ,
  * dW3 = δ3·h2ᵀ, dW2 = δ2·h1ᵀ, dW1 = δ1·xᵀ (each ⊙ its MADE mask), db = row sums of δ.
- * `factors` holds nfx_made_backward_factor_floats(B, d, H) floats.
+ * `factors` holds nfx_made_backward_factor_floats(B, d, H) floats and may hold anything on entry
+ * (every row nfx_made_backward_weights reads is written here, pads included).
  * ------------------------------------------------------------------------------------- */
 int nfx_made_pack_backward(const NfxMlpRaw* net, int d, int H, float* packed, void* stream);
 size_t nfx_made_backward_factor_floats(int64_t B, int d, int H);
@@ -324,7 +341,8 @@ int nfx_made_affine_backward(const float* packed, const float* in, const float* 
  * net.2.bias, net.4.weight, net.4.bias, net.6.weight [2d,H], net.6.bias [2d] — each weight
  * gradient multiplied by its mask (masks[4]: the MaskedLinear `mask` buffers, device, row-major;
  * the gradient of F.linear(a, W * mask, b), masked_linear.py:14-18). `grads` holds
- * nfx_made_param_floats(d, H) floats, `workspace` nfx_made_wgrad_workspace_bytes(B, d, H) bytes.
+ * nfx_made_param_floats(d, H) floats, `workspace` nfx_made_wgrad_workspace_bytes(B, d, H) bytes;
+ * both may hold anything on entry.
  * Replaces the autograd weight-gradient GEMMs of made.py:81-134. */
 /* Backward of the SEQUENTIAL directions (NFX_IAF_INVERSE: inverse_autoregressive_flow.py:65-103,
  * the IAF density direction; NFX_MAF_FORWARD: masked_autoregressive_flow.py:46-78) for
@@ -352,7 +370,8 @@ int nfx_made_backward_weights(const float* factors, int64_t B, int d, int H,
  * data_max rescale, and at most 2 (H <= 32) / 1 (H <= 64) transformed dimensions
  * (NFX_EUNSUPPORTED otherwise). packed: nfx_spline_pack_backward image; grads: fp32, the
  * layer's parameters() order (param_net.0.weight, .0.bias, .2.weight, .2.bias, .4.weight,
- * .4.bias); workspace: nfx_spline_backward_workspace_bytes(B, d, H, K) bytes.
+ * .4.bias); workspace: nfx_spline_backward_workspace_bytes(B, d, H, K) bytes. grads and workspace
+ * may hold anything on entry.
  * ------------------------------------------------------------------------------------- */
 size_t nfx_spline_backward_packed_floats(int d, int H, int K);
 size_t nfx_spline_backward_param_floats(int d, int H, int K);
@@ -391,7 +410,8 @@ int nfx_spline_coupling_backward(const float* packed, const float* mask, const f
  *   nfx_affine_train_assemble                      -> fp32 parameter gradients in the layer's
  *                                                     parameters() order (s_net then b_net)
  * `workspace` holds nfx_affine_train_workspace_bytes(B, d, H) bytes and must be the same buffer
- * for stages 2 and 3 of one backward.
+ * for stages 2 and 3 of one backward. workspace, stats, tpack, epack, G
+ * (nfx_affine_train_grad_doubles doubles) and grads may hold anything on entry.
  * ------------------------------------------------------------------------------------- */
 size_t nfx_affine_train_pack_floats(int d, int H);
 size_t nfx_affine_train_stats_doubles(int H);
@@ -420,7 +440,8 @@ int nfx_affine_train_assemble(const double* G, const double* stats1, const doubl
 /* Kept activations (H <= 64): nfx_affine_train_stats_keep(layer 2, keep) also writes the raw
  * layer-2 pre-activations h2 = W2 a1 + b2 of both nets into `keep` (nfx_affine_train_keep_floats
  * floats, 512 B per sample at H = 64), and nfx_affine_train_backward_keep(stage 1 or 2, keep)
- * reads them instead of recomputing layers 1-2 (keep = NULL: the plain entry points). */
+ * reads them instead of recomputing layers 1-2 (keep = NULL: the plain entry points). `keep` may
+ * hold anything on entry. */
 size_t nfx_affine_train_keep_floats(int64_t B, int d, int H);
 int nfx_affine_train_stats_keep(const float* tpack, const float* in, int64_t B, int d, int H,
                                 int layer, double* stats, void* workspace, float* keep,
@@ -481,7 +502,7 @@ int nfx_gauss_logprob_backward(const float* z, const float* grad_logp, float* gr
  * Autograd of one apply w.r.t. the input and (weight, bias) — the running statistics are
  * buffers — from grad_out [B,d] and grad_log_det [B] (either may be NULL = zero):
  *   nfx_flowbn_backward       grad_in [B,d], grad_gamma [d], grad_beta [d]
- * `workspace` holds nfx_flowbn_workspace_bytes(B, d) bytes.
+ * `workspace` holds nfx_flowbn_workspace_bytes(B, d) bytes and, like stats, may hold anything on entry.
  * ------------------------------------------------------------------------------------- */
 size_t nfx_flowbn_workspace_bytes(int64_t B, int d);
 int nfx_flowbn_apply(const float* in, float* out, float* log_det, const float* gamma, const float* beta,
@@ -517,7 +538,8 @@ int nfx_linear_backward_data(const float* gy, const float* w, const float* wmask
                              const float* out_scale, float* gx, int64_t M, int N, int K, int accumulate, void* stream);
 /* gw[N][K] = (gy^T (x o in_scale)) o wmask, gb[N] = sum over rows of gy (gb may be NULL):
  * autograd's weight and bias gradients of nn.Linear / MaskedLinear, split over the batch into a
- * workspace of nfx_linear_workspace_bytes(M, N, K) bytes and summed in a fixed order. */
+ * workspace of nfx_linear_workspace_bytes(M, N, K) bytes and summed in a fixed order. The
+ * workspace, gw and gb may hold anything on entry. */
 size_t nfx_linear_workspace_bytes(int64_t M, int N, int K);
 int nfx_linear_backward_weight(const float* gy, const float* x, const float* in_scale, const float* wmask, float* gw,
                                float* gb, int64_t M, int N, int K, void* workspace, void* stream);
@@ -572,7 +594,8 @@ int nfx_affine_elem_backward(const float* x, const float* s_raw, const float* b_
  * into mean / invstd / scale = gamma invstd / shift = beta - mean scale (BN(z) = z scale + shift);
  * nfx_bn_apply_relu h = relu(z scale + shift); the backward takes g = dL/dBN-output (ReLU mask
  * applied): nfx_bn_backward_sums sums [2][N] = (sum g = dL/dbeta, sum g xhat = dL/dgamma) in
- * float64 (workspace nfx_bn_workspace_bytes(M, N)); nfx_bn_backward_apply dL/dz (train: the
+ * float64 (workspace nfx_bn_workspace_bytes(M, N), which like sums may hold anything on entry);
+ * nfx_bn_backward_apply dL/dz (train: the
  * batch-statistics terms with the global sample count *count, a device float64 — the n of the
  * merged moments triple). */
 int nfx_bn_prepare(const double* stats, const float* gamma, const float* beta, float* running_mean,
@@ -665,13 +688,13 @@ int nfx_cnf_integrate(const float* packed, const float* in, float* out, float* l
  *                              traj, nfx_cnf_trajectory_floats floats: the state at the start of
  *                              steps 1 .. n-1, step-major [n-1][B][d], then the last step's result
  *                              before the guards, y_n [B][d] and its log-det [B]. Equal times: 0
- *                              floats, traj may be null.
+ *                              floats, traj may be null. traj may hold anything on entry.
  *   nfx_cnf_backward           gx [B, d] and the six parameter gradients in nn.Linear layout (gw1
  *                              [H, d+1], gb1 [H], gw2 [H, H], gb2 [H], gw3 [d, H], gb3 [d];
  *                              overwritten, not accumulated) from the cotangents gy [B, d] and gld
  *                              [B] of (out, log_det), the forward's input `in`, its trajectory and the
- *                              raw w1, w2, w3. workspace: nfx_cnf_backward_workspace_floats floats,
- *                              any content. Three launches: the sweep (one wave per 32-row tile up to
+ *                              raw w1, w2, w3. workspace: nfx_cnf_backward_workspace_floats floats;
+ *                              it may hold anything on entry. Three launches: the sweep (one wave per 32-row tile up to
  *                              nfx_cnf_backward_slots waves, nfx_cnf_backward_block_threads threads per
  *                              workgroup; each wave leaves its partial sums in its own workspace
  *                              slot), the slot reduction in index order, and the finish. No atomics:

@@ -299,6 +299,19 @@ def check(rc, what):
         raise NfxError(f"{what} failed (rc={rc}): {msg}")
 
 
+def dense(t):
+    """`t` in the form the kernels read a caller's tensor in: contiguous row-major, based at a
+    16-byte boundary (x rows of d = 2 / 4 and packed images move as 8- and 16-byte loads). What
+    the allocator hands out already is, and comes back as it is; a strided or transposed view is
+    copied, and so is a contiguous view that starts at an odd float of a larger buffer.
+    `DevicePtr` reads nothing but `data_ptr()`, so every tensor a caller owns passes through here
+    (or `.contiguous()`, for the entry points that take any 4-byte-aligned base) on its way in."""
+    t = t.contiguous()
+    if t.data_ptr() & 15:
+        t = t.clone()
+    return t
+
+
 def ptr(t):
     """Device address of a tensor as a plain int (ctypes c_void_p arguments accept ints)."""
     return None if t is None else t.data_ptr()
@@ -326,7 +339,7 @@ def mlp_raw(linears, batchnorms=(), masks=None):
     keep = []
 
     def p(t):
-        t = t.detach().contiguous().float()
+        t = dense(t.detach().float())
         keep.append(t)
         return t.data_ptr()
 

@@ -135,7 +135,7 @@ class ARQS(HipFlow):
     # -- any-shape path (csrc/nfx_generic.hip): the reference's d steps, MADE on MFMA GEMMs --------
     def _generic_pack(self, device):
         lins = self.conditioner.linears()
-        masks = [lin.mask.detach().to(device=device, dtype=torch.float32).contiguous() for lin in lins]
+        masks = [_lib.dense(lin.mask.detach().to(device=device, dtype=torch.float32)) for lin in lins]
         posts = [None, None, None]
         for i, bn in enumerate(self.conditioner.batchnorms()):
             sc = (bn.weight.detach() / torch.sqrt(bn.running_var.detach() + bn.eps)).float().contiguous()
@@ -183,7 +183,7 @@ class ARQS(HipFlow):
     def _train_forward(self, x, direction):
         """Returns (y, ld, state, bnps, counts): each step's MADE call normalises with the batch
         statistics of the partial state and updates the running statistics (d updates)."""
-        x = x.detach().contiguous()
+        x = _lib.dense(x.detach())
         bounds = self._bounds(x.device)
         xr = x if bounds is None else self._map(x, bounds, 0)
         masks, _ = self._packed(x.device, self._generic_pack, slot="_nfx_generic_pack_cache")
@@ -224,10 +224,10 @@ class ARQS(HipFlow):
         (state, bnps, counts) from _train_forward), its spline row differentiated (nfx_arqs_step
         mode 1: rqs_unit_adjoint), the MADE's weight gradients accumulated and its input VJP added
         into the running state adjoint. With bounds, dL/dstate = gy w and dL/dx = dL/dxr / w."""
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, d = x.shape
-        gy = torch.zeros_like(x) if gy is None else gy.contiguous().float()
-        gld = torch.zeros(B, device=x.device) if gld is None else gld.contiguous().float()
+        gy = torch.zeros_like(x) if gy is None else _lib.dense(gy.float())
+        gld = torch.zeros(B, device=x.device) if gld is None else _lib.dense(gld.float())
         bounds = self._bounds(x.device)
         xr = x if bounds is None else self._map(x, bounds, 0)
         if train is not None:

@@ -150,7 +150,7 @@ class _MadeAffineFlow(HipFlow):
     def _generic_pack(self, device):
         """(masks, eval-BatchNorm post affines) on the device, cached with the parameters."""
         lins = self.conditioner.linears()
-        masks = [lin.mask.detach().to(device=device, dtype=torch.float32).contiguous() for lin in lins]
+        masks = [_lib.dense(lin.mask.detach().to(device=device, dtype=torch.float32)) for lin in lins]
         posts = [None, None, None]
         bns = self.conditioner.batchnorms()
         if bns:
@@ -217,7 +217,7 @@ class _MadeAffineFlow(HipFlow):
         running statistics (so d updates per forward), one element step each; then the guards.
         Returns (y, ld, work, wld, bnps, counts)."""
         L = _lib.checked()
-        x = x.detach().contiguous()
+        x = _lib.dense(x.detach())
         B, d = x.shape
         variant = self._variant(direction)
         st = _lib.stream_of(x)
@@ -265,7 +265,7 @@ class _MadeAffineFlow(HipFlow):
     def _generic_train_forward(self, x, direction):
         """One train-mode MADE call on x (made_bn_train_call: batch moments, SyncBN merge, running
         update, normalisation), then the parallel element map. Returns (y, ld, bnp, counts)."""
-        x = x.detach().contiguous()
+        x = _lib.dense(x.detach())
         B, d = x.shape
         prm, bnp, counts = self._generic_made_bn_train(x)
         y = torch.empty_like(x)
@@ -410,11 +410,11 @@ class _MadeAffineFlow(HipFlow):
         """dL/dx and the parameter gradients (in self.parameters() order) of one call. Batches
         above nfx_made_backward_max_batch (32-bit factor offsets) run in chunks: dL/dx is per
         sample and every parameter gradient is a sum over samples."""
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, d = x.shape
         H = self.conditioner.hidden_dim
-        gz = torch.zeros_like(x) if gz is None else gz.contiguous().float()
-        gld = torch.zeros(B, device=x.device) if gld is None else gld.contiguous().float()
+        gz = torch.zeros_like(x) if gz is None else _lib.dense(gz.float())
+        gld = torch.zeros(B, device=x.device) if gld is None else _lib.dense(gld.float())
         if not self._fused_backward_ok():
             return self._generic_backward(x, gz, gld, direction)
         cap = int(_lib.lib().nfx_made_backward_max_batch(d, H))
@@ -449,7 +449,7 @@ class _MadeAffineFlow(HipFlow):
         dev = fac.device
         grads = torch.empty(L.nfx_made_param_floats(d, H), device=dev, dtype=torch.float32)
         ws = torch.empty(max(1, L.nfx_made_wgrad_workspace_bytes(B, d, H)), device=dev, dtype=torch.uint8)
-        masks = [lin.mask.to(device=dev, dtype=torch.float32).contiguous() for lin in self.conditioner.linears()]
+        masks = [_lib.dense(lin.mask.to(device=dev, dtype=torch.float32)) for lin in self.conditioner.linears()]
         mp = (ctypes.c_void_p * 4)(*[m.data_ptr() for m in masks])
         with timed(BACKWARD_EVENTS, "made_wgrad_kernel"):
             L.nfx_made_backward_weights(fac, B, d, H, mp, grads, ws, _lib.stream_of(fac))
@@ -539,9 +539,9 @@ class _MadeTrainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, gld):
         (x,) = ctx.saved_tensors
-        x = x.detach().contiguous()
-        gy = torch.zeros_like(x) if gy is None else gy.contiguous().float()
-        gld = torch.zeros(x.shape[0], device=x.device) if gld is None else gld.contiguous().float()
+        x = _lib.dense(x.detach())
+        gy = torch.zeros_like(x) if gy is None else _lib.dense(gy.float())
+        gld = torch.zeros(x.shape[0], device=x.device) if gld is None else _lib.dense(gld.float())
         gx, grads = ctx.layer._generic_bn_backward(x, gy, gld, ctx.direction, ctx.bnp, ctx.counts)
         STATS["hip"] += 1
         params = list(ctx.layer.parameters())
@@ -563,9 +563,9 @@ class _MadeSeqTrainFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy, gld):
         x, work, wld = ctx.saved_tensors
-        x = x.detach().contiguous()
-        gy = torch.zeros_like(x) if gy is None else gy.contiguous().float()
-        gld = torch.zeros(x.shape[0], device=x.device) if gld is None else gld.contiguous().float()
+        x = _lib.dense(x.detach())
+        gy = torch.zeros_like(x) if gy is None else _lib.dense(gy.float())
+        gld = torch.zeros(x.shape[0], device=x.device) if gld is None else _lib.dense(gld.float())
         gx, grads = ctx.layer._generic_seq_train_backward(x, gy, gld, ctx.direction, work, wld, ctx.bnps, ctx.counts)
         STATS["hip"] += 1
         params = list(ctx.layer.parameters())

@@ -184,7 +184,7 @@ class ContinuousFlow(HipFlow):
         L = _lib.checked()
         d, H = self.dim, self.hidden_dim
         packed = torch.empty(L.nfx_cnf_packed_floats(d, H), device=device, dtype=torch.float32)
-        t = [p.detach().to(device=device, dtype=torch.float32).contiguous()
+        t = [_lib.dense(p.detach().to(device=device, dtype=torch.float32))
              for lin in self.ode_func.linears() for p in (lin.weight, lin.bias)]
         L.nfx_cnf_pack(*t, d, H, packed, _lib.stream_of(packed))
         return packed
@@ -218,7 +218,7 @@ class ContinuousFlow(HipFlow):
         return packed
 
     def _raw_weights(self, device):
-        return [p.detach().to(device=device, dtype=torch.float32).contiguous()
+        return [_lib.dense(p.detach().to(device=device, dtype=torch.float32))
                 for lin in self.ode_func.linears() for p in (lin.weight, lin.bias)]
 
     def _time_args(self, direction):
@@ -229,7 +229,7 @@ class ContinuousFlow(HipFlow):
         """(y, ld, traj): the forward kernel's outputs, bit for bit, and the trajectory the backward
         replays (the state at the start of every step, and the unclamped final state)."""
         L = _lib.checked()
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, d, H = x.shape[0], self.dim, self.hidden_dim
         t0, t1, step = self._time_args(direction)
         packed = self._packed(x.device, self._build_backward_pack, slot="_nfx_bwd_pack_cache")
@@ -243,15 +243,15 @@ class ContinuousFlow(HipFlow):
         """(gx, [gW1, gb1, gW2, gb2, gW3, gb3]) in HIP only; `traj` is the saving forward's
         trajectory (recomputed here when the caller kept none)."""
         L = _lib.checked()
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, d, H = x.shape[0], self.dim, self.hidden_dim
         if traj is None:
             traj = self._hip_forward_save(x, direction)[2]
         t0, t1, step = self._time_args(direction)
         packed = self._packed(x.device, self._build_backward_pack, slot="_nfx_bwd_pack_cache")
         w1, _, w2, _, w3, _ = raw = self._raw_weights(x.device)
-        gy = gy.to(torch.float32).contiguous()
-        gld = gld.to(torch.float32).contiguous()
+        gy = _lib.dense(gy.to(torch.float32))
+        gld = _lib.dense(gld.to(torch.float32))
         gx = torch.empty_like(x)
         grads = [torch.empty_like(t) for t in raw]
         ws = torch.empty(L.nfx_cnf_backward_workspace_floats(B, d, H), device=x.device, dtype=torch.float32)
@@ -268,6 +268,7 @@ class _CnfFunction(torch.autograd.Function):
     def forward(ctx, layer, direction, x, *params):
         from . import flow as _flow
         _flow.STATS["hip"] += 1
+        x = _lib.dense(x)  # (saved in this form: a strided or offset input is copied once, not per pass)
         with torch.no_grad():
             y, ld, traj = layer._hip_forward_save(x.detach(), direction)
         ctx.layer, ctx.direction = layer, direction

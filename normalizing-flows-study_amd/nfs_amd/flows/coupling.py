@@ -165,6 +165,7 @@ class _CouplingTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layer, direction, x, *params):
+        x = _lib.dense(x)  # (saved in this form: a strided or offset input is copied once, not per pass)
         y, ld, tpack, stats = layer._train_forward(x, direction, keep=True)
         ctx.layer = layer
         ctx.direction = direction
@@ -273,7 +274,7 @@ class CouplingLayer(HipFlow):
         return _generic.bn_eval_params([self.s_net[1], self.s_net[4], self.b_net[1], self.b_net[4]], device)
 
     def _mask_dev(self, device):
-        return self.mask.detach().to(device=device, dtype=torch.float32).contiguous()
+        return _lib.dense(self.mask.detach().to(device=device, dtype=torch.float32))
 
     def _generic_launch(self, x, out, log_det, direction, accumulate):
         mask = self._mask_dev(x.device)
@@ -303,7 +304,7 @@ class CouplingLayer(HipFlow):
         """Train mode on the any-shape path: per conditioner BatchNorm the batch moments
         (nfx_flowbn_moments, SyncBN-merged), mean/invstd/scale/shift and the running update
         (nfx_bn_prepare), then the affine element map. Returns (y, ld, bnp, counts)."""
-        x = x.detach().contiguous()
+        x = _lib.dense(x.detach())
         B, d = x.shape
         mask = self._mask_dev(x.device)
         bnp, counts, raw = [], [], []
@@ -380,7 +381,7 @@ class CouplingLayer(HipFlow):
         if not self._fused_train():
             return self._generic_train_forward(x, direction)
         L = _lib.checked()
-        x = x.detach().contiguous()
+        x = _lib.dense(x.detach())
         B, d = x.shape
         H = self._hidden()
         dev = x.device
@@ -467,9 +468,9 @@ class CouplingLayer(HipFlow):
 
     def _hip_backward(self, x, gy, gld, direction):
         if not self._fused_train():
-            x = x.contiguous()
-            gy = torch.zeros_like(x) if gy is None else gy.contiguous().float()
-            gld = torch.zeros(x.shape[0], device=x.device) if gld is None else gld.contiguous().float()
+            x = _lib.dense(x)
+            gy = torch.zeros_like(x) if gy is None else _lib.dense(gy.float())
+            gld = torch.zeros(x.shape[0], device=x.device) if gld is None else _lib.dense(gld.float())
             bnp = self._packed(x.device, self._generic_bn_eval, slot="_nfx_generic_pack_cache")
             return self._generic_backward(x, gy, gld, direction, bnp, None)
         tpack, stats = self._packed(x.device, self._build_eval_backward_pack, slot="_nfx_evalbwd_pack_cache")
@@ -479,13 +480,13 @@ class CouplingLayer(HipFlow):
         """dL/dx and the parameter gradients (parameters() order) of one train-mode call
         (sync=False: eval mode, the BatchNorm sums are plain parameter-gradient partials)."""
         L = _lib.checked()
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, d = x.shape
         H = self._hidden()
         dev = x.device
         st = _lib.stream_of(x)
-        gy = torch.zeros_like(x) if gy is None else gy.contiguous().float()
-        gld = torch.zeros(B, device=dev) if gld is None else gld.contiguous().float()
+        gy = torch.zeros_like(x) if gy is None else _lib.dense(gy.float())
+        gld = torch.zeros(B, device=dev) if gld is None else _lib.dense(gld.float())
         if not self._fused_train():  # tpack, stats = the any-shape path's (bnp, counts)
             return self._generic_backward(x, gy, gld, direction, tpack, stats)
         G = torch.empty(L.nfx_affine_train_grad_doubles(d, H), device=dev, dtype=torch.float64)

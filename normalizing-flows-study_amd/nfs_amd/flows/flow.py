@@ -19,6 +19,8 @@ silently running eager (set nfs_amd.flows.flow.ALLOW_TORCH_FALLBACK = True to pe
 import torch
 import torch.nn as nn
 
+from .. import _lib
+
 ALLOW_TORCH_FALLBACK = False
 
 # Counters so tests and the bench can prove which path ran.
@@ -87,6 +89,7 @@ class HipFlowFunction(torch.autograd.Function):
     def forward(ctx, layer, direction, x, *params):
         ctx.layer = layer
         ctx.direction = direction
+        x = _lib.dense(x)  # (saved in this form: a strided or offset input is copied once, not per pass)
         ctx.save_for_backward(x)
         with torch.no_grad():
             y, ld = layer._hip_call(x, direction)
@@ -164,7 +167,7 @@ class HipFlow(Flow):
         return self._hip_call(x, direction)
 
     def _hip_call(self, x, direction):
-        x = x.contiguous()
+        x = _lib.dense(x)
         out = torch.empty_like(x)
         ld = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
         self._hip_launch_counted(x, out, ld, direction, accumulate=False)
@@ -290,7 +293,7 @@ class SequentialFlow(Flow):
         return all(isinstance(f, HipFlow) and f._route(x) == "hip" for f in self.flows)
 
     def _hip_chain(self, x, direction):
-        x = x.contiguous()
+        x = _lib.dense(x)
         ld = torch.zeros(x.shape[0], device=x.device, dtype=torch.float32)
         from . import coupling as _coupling
         from . import spline as _spline

@@ -10,14 +10,23 @@ import torch
 from .. import _lib
 
 
+def _rows(t):
+    """A caller's tensor as the GEMM kernels index it: row-major with no gaps. `DevicePtr` passes
+    `data_ptr()` alone, so a transposed or strided view (an nn.Linear whose weight is the
+    transpose of another tensor, a column slice) would be read as if it were dense. The
+    nfx_linear_* kernels take any 4-byte-aligned base, so an aligned copy is not needed. A no-op
+    for what is contiguous already."""
+    return None if t is None else t.contiguous()
+
+
 def linear_forward(x, lin, in_scale=None, relu=False, wmask=None, post=None):
     """relu?(((x * in_scale) @ (lin.weight * wmask).T + lin.bias) * post[0] + post[1]) — one
     nn.Linear / MaskedLinear (+ folded eval BatchNorm, + ReLU) on MFMA."""
     M, K = x.shape
     N = lin.out_features
     y = torch.empty(M, N, device=x.device, dtype=torch.float32)
-    w = lin.weight.detach()
-    b = None if lin.bias is None else lin.bias.detach()
+    x, w, wmask = _rows(x), _rows(lin.weight.detach()), _rows(wmask)
+    b = None if lin.bias is None else _rows(lin.bias.detach())
     ps, pt = (None, None) if post is None else post
     _lib.checked().nfx_linear_forward(x, w, wmask, b, in_scale, ps, pt, y, M, K, N, int(bool(relu)),
                                       _lib.stream_of(x))
@@ -32,8 +41,10 @@ def linear_backward_data(gy, lin, act=None, out_scale=None, out=None, wmask=None
     acc = out is not None
     if out is None:
         out = torch.empty(M, K, device=gy.device, dtype=torch.float32)
-    _lib.checked().nfx_linear_backward_data(gy, lin.weight.detach(), wmask, act, out_scale, out, M, N, K, int(acc),
-                                            _lib.stream_of(gy))
+    elif not out.is_contiguous():
+        raise ValueError("linear_backward_data: `out` is added into in place and must be contiguous")
+    _lib.checked().nfx_linear_backward_data(_rows(gy), _rows(lin.weight.detach()), _rows(wmask), _rows(act),
+                                            out_scale, out, M, N, K, int(acc), _lib.stream_of(gy))
     return out
 
 
@@ -46,7 +57,7 @@ def linear_backward_weight(gy, x, lin, in_scale=None, wmask=None):
     gw = torch.empty(N, K, device=gy.device, dtype=torch.float32)
     gb = None if lin.bias is None else torch.empty(N, device=gy.device, dtype=torch.float32)
     ws = torch.empty(max(1, L.nfx_linear_workspace_bytes(M, N, K)), device=gy.device, dtype=torch.uint8)
-    L.nfx_linear_backward_weight(gy, x, in_scale, wmask, gw, gb, M, N, K, ws, _lib.stream_of(gy))
+    L.nfx_linear_backward_weight(_rows(gy), _rows(x), in_scale, _rows(wmask), gw, gb, M, N, K, ws, _lib.stream_of(gy))
     return gw, gb
 
 

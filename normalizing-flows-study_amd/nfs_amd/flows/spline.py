@@ -245,7 +245,7 @@ class SplineCouplingLayer(HipFlow):
 
     def _mask_dev(self, device):
         m = self.mask
-        return m.detach().to(device=device, dtype=torch.float32).contiguous()
+        return _lib.dense(m.detach().to(device=device, dtype=torch.float32))
 
     def _generic_params(self, x, bounds=None):
         """Conditioner recompute on the any-shape path: (mask, conditioner input, h1, h2, params
@@ -345,11 +345,11 @@ class SplineCouplingLayer(HipFlow):
         """dL/dx and the parameter gradients (parameters() order) of one forward/inverse call:
         nfx_spline_coupling_backward (MLP recompute, spline adjoint, data-gradient chain and the
         weight-gradient contractions in one kernel, then a fixed-order workgroup reduction)."""
-        x = x.contiguous()
+        x = _lib.dense(x)
         B, d = x.shape
         H, K = self._hidden(), self.num_bins
-        gy = torch.zeros_like(x) if gy is None else gy.contiguous().float()
-        gld = torch.zeros(B, device=x.device) if gld is None else gld.contiguous().float()
+        gy = torch.zeros_like(x) if gy is None else _lib.dense(gy.float())
+        gld = torch.zeros(B, device=x.device) if gld is None else _lib.dense(gld.float())
         if not self._fused_backward_ok():
             return self._generic_backward(x, gy, gld, direction)
         packed, mask = self._packed(x.device, self._build_bwd_pack, slot="_nfx_bwd_pack_cache")

@@ -128,7 +128,7 @@ class NormalizingFlowModel(nn.Module):
         inverse chain), the last layer also writes the Gaussian log-density and float64 NLL
         partials in its epilogue when it has a fused variant; `fused` in the return says
         whether it did."""
-        x = x.contiguous()
+        x = _lib.dense(x)
         B = x.shape[0]
         ld = torch.empty(B, device=x.device, dtype=torch.float32)
         n = len(self.flows)
@@ -193,8 +193,9 @@ class NormalizingFlowModel(nn.Module):
 
         With return_sums=True also returns a float64 tensor [sum_i log p(x_i), B] on x's device
         (the partial a data-parallel NLL all-reduces). `workspace`: the fused epilogue's float64
-        partials + arrival word (uint8 tensor of at least nfx_gauss_workspace_bytes(B) bytes, any
-        content: ABI 3 tags the arrival word per launch); by default one cached per (device,
+        partials + arrival word (a contiguous uint8 tensor of at least nfx_gauss_workspace_bytes(B)
+        bytes based at a 16-byte boundary, else ValueError; any content: ABI 3 tags the arrival
+        word per launch); by default one cached per (device,
         current stream), so calls on different streams never share one."""
         if self._hip_chain_ok(x) and len(self.flows) > 0:
             B = x.shape[0]
@@ -300,7 +301,8 @@ class NormalizingFlowModel(nn.Module):
         nfx_spline_chain_sample). Stacks that start with an IAF layer: the draw in that layer's
         kernel (nfx_made_affine_sample), the remaining layers launched one by one — L launches
         for L layers. Returns (x, log_det, z); x and log_det equal forward(z) bit for bit.
-        out=(z, x, ld) writes into caller buffers (GraphedFlow(mode="sample")). Calls sharing
+        out=(z, x, ld) writes into caller buffers (GraphedFlow(mode="sample")): contiguous, each
+        based at a 16-byte boundary (the kernels write them in place; ValueError otherwise). Calls sharing
         this model's generator state must be stream-ordered."""
         dev = _cuda_device(device)
         if not self.sample_fused_ok(num_samples, dev):
@@ -314,6 +316,8 @@ class NormalizingFlowModel(nn.Module):
             ld = torch.empty(num_samples, device=dev)
         else:
             z, x, ld = out
+            if any(not t.is_contiguous() or t.data_ptr() & 15 for t in out):
+                raise ValueError("sample_fused: out = (z, x, ld) must be contiguous, each based at a 16-byte boundary")
         chain = self._sample_chain(num_samples, dev)
         if chain is not None:
             chain.chain_sample(list(self.flows), state, seed, z, x, ld)
@@ -343,7 +347,8 @@ class NormalizingFlowModel(nn.Module):
         z. Between-layer BatchNorm in eval mode is a fixed map and is fine. Raises
         NotImplementedError only where forward itself would leave the HIP kernels (train-mode
         BatchNorm, a CPU device). Returns (x, log_det, z).
-        out=(z, x, ld): caller buffers; x and ld may be None (outside the fused path they are
+        out=(z, x, ld): caller buffers (contiguous, based at a 16-byte boundary, else ValueError);
+        x and ld may be None (outside the fused path they are
         then the forward chain's own outputs, which saves two copies). Calls sharing this model's
         generator state must be stream-ordered."""
         dev = _cuda_device(device)
@@ -359,8 +364,10 @@ class NormalizingFlowModel(nn.Module):
         seed, state = self._sampler_state(dev)
         d = self.flows[0].data_dim
         z = torch.empty(num_samples, d, device=dev) if out is None else out[0]
-        if z.shape != (num_samples, d) or z.dtype != torch.float32 or z.device != dev or not z.is_contiguous():
-            raise ValueError(f"sample_on_device: z must be a contiguous fp32 [{num_samples}, {d}] tensor on {dev}")
+        if (z.shape != (num_samples, d) or z.dtype != torch.float32 or z.device != dev or not z.is_contiguous()
+                or z.data_ptr() & 15):
+            raise ValueError(f"sample_on_device: z must be a contiguous fp32 [{num_samples}, {d}] tensor on {dev}, "
+                             "based at a 16-byte boundary")
         _lib.checked().nfx_base_normal(seed & ((1 << 64) - 1), state, z, num_samples, d, _lib.stream_of(z))
         STATS["hip"] += 1
         with torch.no_grad():
@@ -431,12 +438,14 @@ def check_gauss_workspace(ws, B, device):
     n = _lib.lib().nfx_gauss_workspace_bytes(B)
     if ws.dtype != torch.uint8 or ws.device != torch.device(device) or ws.numel() < n or not ws.is_contiguous():
         raise ValueError(f"log_prob workspace: need a contiguous uint8 tensor of >= {n} bytes on {device}")
+    if ws.data_ptr() & 15:  # float64 partials: a byte view at an odd offset of a larger buffer will not do
+        raise ValueError("log_prob workspace: need a tensor based at a 16-byte boundary")
     return ws
 
 
 def gauss_logprob(z, ld, logp=None, sums=None, ws=None):
     """Fused `MultivariateNormal(0,I).log_prob(z) + ld` and float64 [sum, count] (nfx_gauss_logprob)."""
-    z = z.contiguous()
+    z, ld = _lib.dense(z), _lib.dense(ld)
     B, d = z.shape
     if logp is None:
         logp = torch.empty(B, device=z.device, dtype=torch.float32)
@@ -454,8 +463,8 @@ class _GaussLogProbFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, ld, workspace):
-        z = z.contiguous()
-        logp, sums = gauss_logprob(z, ld.contiguous(), ws=workspace)
+        z = _lib.dense(z)
+        logp, sums = gauss_logprob(z, _lib.dense(ld), ws=workspace)
         ctx.save_for_backward(z)
         ctx.mark_non_differentiable(sums)
         return logp, sums
@@ -464,7 +473,7 @@ class _GaussLogProbFn(torch.autograd.Function):
     def backward(ctx, g, _gs):
         (z,) = ctx.saved_tensors
         B, d = z.shape
-        g = g.contiguous().float()
+        g = _lib.dense(g.float())
         gz, gld = torch.empty_like(z), torch.empty_like(g)
         _lib.checked().nfx_gauss_logprob_backward(z, g, gz, gld, B, d, _lib.stream_of(z))
         STATS["hip"] += 1
@@ -496,7 +505,7 @@ def _bn_workspace(B, d, device):
 def _bn_update_running_hip(bn, x):
     """Train mode (normalizing_flow_model.py:74-79): fold the batch moments of x into the running
     statistics; with SyncBN enabled the moments are those of every rank's shard."""
-    x = x.detach().contiguous()
+    x = _lib.dense(x.detach())
     B, d = x.shape
     L = _lib.checked()
     stats = torch.empty(d, 3, device=x.device, dtype=torch.float64)
@@ -537,7 +546,7 @@ class _FlowBatchNormFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ld, weight, bias, bn, direction):
-        x = x.contiguous()
+        x = _lib.dense(x)
         y = torch.empty_like(x)
         ld_out = ld.detach().to(torch.float32).contiguous().clone()
         _bn_launch(bn, x, y, ld_out, direction)
@@ -553,8 +562,8 @@ class _FlowBatchNormFn(torch.autograd.Function):
         gx = torch.empty_like(x)
         dg = torch.empty(d, device=x.device, dtype=torch.float32)
         db = torch.empty(d, device=x.device, dtype=torch.float32)
-        gy = gy.contiguous() if gy is not None else None
-        gld_c = gld.contiguous() if gld is not None else None
+        gy = _lib.dense(gy) if gy is not None else None
+        gld_c = _lib.dense(gld) if gld is not None else None
         ws = _bn_workspace(B, d, x.device)
         _lib.checked().nfx_flowbn_backward(x, gy, gld_c, gx, weight.detach(), bias.detach(), rm, rv, ctx.eps, dg, db,
                                            B, d, ctx.direction, ws, _lib.stream_of(x))
