@@ -79,7 +79,7 @@ __global__ void affine_pack_kernel(NfxMlpRaw s_net, NfxMlpRaw b_net, const float
 // round-to-nearest bf16 pieces in v_mfma_f32_32x32x16_bf16 A-operand order, and the safety words (W2 finite,
 // |w| <= 1e6 and the lower-edge bound below; xsafe = (1e30 - max|b1|) / max_row sum|w1|). One
 // workgroup: the maxima are reductions and the tail is ~14k floats.
-__global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, int d, int H) {
+__global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, int d, int H, int live_fold) {
     const int HT = (H + 31) / 32, KS1 = (d + 1) / 2;
     const AffineLayout L = affine_layout(d, HT);
     const AffineSplit S = affine_split(d, HT);
@@ -186,16 +186,48 @@ __global__ __launch_bounds__(1024) void affine_split_pack_kernel(float* packed, 
             for (int j = 0; j < 8; ++j) r3 = fmaxf(r3, w3sum[net * 8 + j]);
             lost = lost || !(0x1p-133 * (double)r2 * (double)r3 < 0x1p-24);
         }
-        out[S.ok] = (w2_bad || lost) ? 0.f : 1.f;
+        const bool wok = !(w2_bad || lost);
+        out[S.ok] = wok ? 1.f : 0.f;
         out[S.ok + 1] = xs > 0.f ? xs : 0.f;
-        out[S.ok + 2] = 0.f;
-        out[S.ok + 3] = 0.f;
+        // Live outputs (affine_live_unit, nfx_affine_kernel.h): output j with mask[j] == 1.0f exactly
+        // is dead, it enters the layer's result only times (1 - m) = +0. A kernel may skip the fold of the dead rows when
+        // the live ones fit (D + 1) / 2 slots and no dead s or t can be NaN or inf on a tile that
+        // runs the split nets: there every layer-1 activation is <= 1e30 (xsafe), so a layer-2
+        // one is at most hmax = 1e30 * max row-sum|w2| + max|b2| (ok[0] holds, so the split's own
+        // error is far below the margin), and every partial sum of dead row j stays under
+        // row-sum|w3[j]| * hmax + |b3[j]|, required <= 1e37 (NaN or inf sums fail the test).
+        int nlive = 0;
+        uint32_t idx = 0x88888888u;  // slot jj: nibble jj = the output's index; 8 = unused (reads row 0)
+        bool dead_ok = wok && xs > 0.f && live_fold;
+        for (int j = 0; j < d; ++j) {
+            if (packed[L.mask + j] == 1.0f) {
+                for (int net = 0; net < 2; ++net) {
+                    const float* P = packed + net * L.net;
+                    float r2 = 0.f, b2 = 0.f;
+                    for (int i = 0; i < 64; ++i) r2 = fmaxf(r2, w2sum[net * 64 + i]);
+                    for (int i = 0; i < HT * 32; ++i) b2 = fmaxf(b2, fabsf(P[L.b2 + i]));
+                    const double hmax = 1e30 * (double)r2 + (double)b2;
+                    dead_ok = dead_ok && (double)w3sum[net * 8 + j] * hmax + (double)fabsf(P[L.b3 + j]) <= 1e37;
+                }
+            } else {
+                if (nlive < 8) idx = (idx & ~(0xfu << (4 * nlive))) | ((uint32_t)j << (4 * nlive));
+                ++nlive;
+                // a live s that is zero by construction (a fresh layer's output weights are): the sign of
+                // a zero log-det would hang on the dead outputs (affine_nets_split), so no elision
+                if (w3sum[j] == 0.f && packed[L.b3 + j] == 0.f) dead_ok = false;
+            }
+        }
+        const bool elide = dead_ok && nlive >= 1 && nlive <= (d + 1) / 2;
+        out[S.ok + 2] = __uint_as_float((uint32_t)nlive | (elide ? kAffineLiveElide : 0u));
+        out[S.ok + 3] = __uint_as_float(idx);
     }
 }
 
 int affine_split_pack(float* packed, int d, int H, hipStream_t s) {
     if (!affine_has_split(d, (H + 31) / 32)) return NFX_OK;
-    affine_split_pack_kernel<<<1, 1024, 0, s>>>(packed, d, H);
+    // NFX_AFFINE_LIVE_FOLD=0 (debugging, tests): no layer packed from now on skips dead outputs
+    const char* e = getenv("NFX_AFFINE_LIVE_FOLD");
+    affine_split_pack_kernel<<<1, 1024, 0, s>>>(packed, d, H, e && atoi(e) == 0 ? 0 : 1);
     return check_launch("affine_split_pack_kernel");
 }
 

@@ -33,7 +33,13 @@ struct AffineLayout {
 // ok[0] = 1 when every W2 entry is finite with |w| <= 1e6 and the activation bits cut below the
 // smallest bf16 subnormal cannot move s by 2^-24 (2^-133 * max row-sum|w2| * max row-sum|w3| <
 // 2^-24), ok[1] = xsafe, the largest |x * m| for which every layer-1 activation stays <= 1e30 (so
-// no bf16 piece product or layer-2 partial sum can overflow).
+// no bf16 piece product or layer-2 partial sum can overflow). The other two words (raw bits) name
+// the LIVE outputs, those with mask[j] != 1.0f; a dead one enters the layer's result only times
+// (1 - m) = +0: ok[2] = their count, | kAffineLiveElide when a kernel may skip the fold of the dead
+// rows (the live ones fit (D + 1) / 2 slots; no dead s or t can be NaN or inf on a tile that runs
+// the split nets: affine_split_pack_kernel); ok[3] = nibble jj: the output of live slot jj, 8 for
+// an unused slot.
+constexpr uint32_t kAffineLiveElide = 0x100u;
 struct AffineSplit {
     int w1, b1, b2, w3, b3, w2s, net, mask, ok, total;
 };
@@ -286,11 +292,18 @@ constexpr int kSplitTermW[6] = {2, 1, 0, 1, 0, 0}, kSplitTermX[6] = {0, 1, 2, 0,
 // is ~230 live VGPRs (two stages' accumulators while the fold drains, 128; the next stage's layer
 // 1, 32; two blocks' operands, 72), hence 8 waves per workgroup (2 per SIMD) in the streaming
 // chain, the only caller (affine_nets_split<..., PIPE = true>).
-template <int HT, int D, int TILES>
+//
+// LIVE: the output-layer fold (w3_quads, fold_fma, the half-wave combine) runs over the layer's
+// live outputs only, NJ = (D + 1) / 2 slots whose W3 rows live_idx names (the tail's ok[3],
+// wave-uniform), and dead sv / bv are +0. A live output takes the same products in the same
+// order as in the full fold. The caller decides when the dead ones cannot show in the result
+// (affine_live_unit).
+template <int HT, int D, int TILES, bool LIVE>
 __device__ __forceinline__ void affine_nets_split_pipe(const float* __restrict__ S, const AffineSplit& SL,
                                                        const float (&xb)[2][(D + 1) / 2], float (&sv)[D],
-                                                       float (&bv)[D]) {
+                                                       float (&bv)[D], uint32_t live_idx) {
     constexpr int KS1 = (D + 1) / 2;
+    constexpr int NJ = LIVE ? (D + 1) / 2 : D;  // folded outputs
     constexpr int NS = 2 * TILES;             // stages: net s / TILES, sample tile s % TILES
     constexpr int KB = 2 * HT;                // k blocks per stage
     constexpr int NT = NFX_SPLIT_TERMS;
@@ -311,13 +324,16 @@ __device__ __forceinline__ void affine_nets_split_pipe(const float* __restrict__
     u32x4 xp[NS * KB][3];       // ... packed: the block's B operands
     u32x4 w[NS * KB][HT][3];    // the block's A operands
     f32x16 hi[NS][HT], lo[NS][HT];
-    f32x4 w3q[NS][HT][D][4];
+    f32x4 w3q[NS][HT][NJ][4];
     float r1[NS * KB][8], tf[NS][NFI];
-    float part[2][D][2];
+    float part[2][NJ][2];
+    int w3row[NJ];  // float offset of slot j's W3 row
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) w3row[j] = (LIVE ? (int)((live_idx >> (4 * j)) & 7u) : j) * HT * 32;
 #pragma unroll
     for (int n = 0; n < 2; ++n)
 #pragma unroll
-        for (int j = 0; j < D; ++j) part[n][j][0] = part[n][j][1] = 0.f;
+        for (int j = 0; j < NJ; ++j) part[n][j][0] = part[n][j][1] = 0.f;
 
     auto base = [&](int s) __attribute__((always_inline)) {
         Sn[s] = S + (s / TILES) * SL.net + opaque_zero();
@@ -361,8 +377,8 @@ __device__ __forceinline__ void affine_nets_split_pipe(const float* __restrict__
     };
     auto w3_quads = [&](int s, int hto, int rq) __attribute__((always_inline)) {
 #pragma unroll
-        for (int j = 0; j < D; ++j)
-            w3q[s][hto][j][rq] = *reinterpret_cast<const f32x4*>(Sn[s] + SL.w3 + (j * HT + hto) * 32 + 16 * h + 4 * rq);
+        for (int j = 0; j < NJ; ++j)
+            w3q[s][hto][j][rq] = *reinterpret_cast<const f32x4*>(Sn[s] + SL.w3 + w3row[j] + hto * 32 + 16 * h + 4 * rq);
     };
     auto fold_relu = [&](int s, int f) __attribute__((always_inline)) {
         tf[s][f] = trelu(hi[s][f / 16][f % 16] + lo[s][f / 16][f % 16]);
@@ -370,7 +386,7 @@ __device__ __forceinline__ void affine_nets_split_pipe(const float* __restrict__
     auto fold_fma = [&](int s, int f) __attribute__((always_inline)) {
         const int hto = f / 16, r = f % 16;
 #pragma unroll
-        for (int j = 0; j < D; ++j)
+        for (int j = 0; j < NJ; ++j)
             part[s / TILES][j][s % TILES] = fmaf(w3q[s][hto][j][r / 4][r % 4], tf[s][f], part[s / TILES][j][s % TILES]);
     };
     // the gap of the following stage in which the fmas of fold item f run, together with its
@@ -447,11 +463,47 @@ __device__ __forceinline__ void affine_nets_split_pipe(const float* __restrict__
         fold_relu(NS - 1, f);
         fold_fma(NS - 1, f);
     }
+    if constexpr (LIVE) {
 #pragma unroll
-    for (int j = 0; j < D; ++j) {
-        sv[j] = tclamp(halves_sum(part[0][j][0], part[0][j][1]) + Sn[0][SL.b3 + j], -10.f, 10.f);
-        bv[j] = tclamp(halves_sum(part[1][j][0], part[1][j][1]) + Sn[NS - 1][SL.b3 + j], -10.f, 10.f);
+        for (int j = 0; j < D; ++j) sv[j] = bv[j] = 0.f;
+#pragma unroll
+        for (int jj = 0; jj < NJ; ++jj) {
+            const int o = (int)((live_idx >> (4 * jj)) & 15u);  // 8: unused slot, matches no output
+            const float s = tclamp(halves_sum(part[0][jj][0], part[0][jj][1]) + Sn[0][SL.b3 + (o & 7)], -10.f, 10.f);
+            const float b = tclamp(halves_sum(part[1][jj][0], part[1][jj][1]) + Sn[NS - 1][SL.b3 + (o & 7)], -10.f, 10.f);
+#pragma unroll
+            for (int j = 0; j < D; ++j) {
+                sv[j] = o == j ? s : sv[j];
+                bv[j] = o == j ? b : bv[j];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+            sv[j] = tclamp(halves_sum(part[0][j][0], part[0][j][1]) + Sn[0][SL.b3 + j], -10.f, 10.f);
+            bv[j] = tclamp(halves_sum(part[1][j][0], part[1][j][1]) + Sn[NS - 1][SL.b3 + j], -10.f, 10.f);
+        }
     }
+}
+
+// Whether a unit may skip the fold of the layer's dead outputs (mask[j] == 1, so the coordinate is
+// an input of the nets and passes through: v = x + (+0) * t). Skipping sets s = b = +0 there,
+// which leaves every bit as it was unless the +0 product decides one: x = -0.0 (the sign of
+// 0 * t picks -0 or +0), or |x| so large that t = (x - b) * exp(-s) overflows (0 * inf = NaN, then
+// y = 0): with |s|, |b| <= 10 it cannot while |x| <= 1e33, as (1e33 + 10) * e^10 < FLT_MAX.
+// (The log-det term of a dead output is +-0: affine_nets_split.)
+// xb: the unit's layer-1 operands x * m (exactly x where m == 1; +0 on inactive lanes), mkb their
+// mask entries. One ballot per unit, beside xsafe's and apart from it: xsafe moves tiles between
+// the split and the fp32 nets, this only chooses between two forms of the same split nets.
+template <int KS1>
+__device__ __forceinline__ bool affine_live_unit(const float (&xb)[2][KS1], const float (&mkb)[KS1]) {
+    bool bad = false;
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int ks = 0; ks < KS1; ++ks)
+            bad = bad || (mkb[ks] == 1.f && (!(fabsf(xb[st][ks]) <= 1e33f) || __float_as_uint(xb[st][ks]) == 0x80000000u));
+    return __builtin_amdgcn_ballot_w64(bad) == 0;
 }
 
 // The straight (not pipelined) form, which the per-layer kernel and the chain shapes outside
@@ -543,11 +595,19 @@ __host__ __device__ constexpr bool affine_split_piped(int HT, int D) { return HT
 // the layer's W2 is unsafe — the fp32 nets (affine_net) from the layer's fp32 image Pg in global
 // memory, whose results replace the split ones on that tile's lanes (lane l holds sample
 // ub + l: tile l >> 5). The choice is per 32-aligned tile, so a row's bits never depend on
-// rows outside its tile.
+// rows outside its tile. live (wave-uniform; PIPE only): fold the live outputs alone, live_idx
+// naming them (affine_live_unit and the layer's kAffineLiveElide allow it); the fp32 nets of a
+// fallback tile compute every output as before. One more thing can show a dead output: the sign
+// of a ZERO log-det. When every term (1 - m_j) * s_j of a sample is +-0, the sum's sign is
+// whatever the dead terms' signs and the compiled order of the adds make it (with one nonzero
+// live term, or a cancellation, which rounds to +0, they cannot matter). The pack refuses layers
+// where that is structural (no live output, or a live row of the s net all zero); where it
+// happens by accident in any lane, the unit runs the full fold after the live one.
 template <int HT, int D, int TILES, bool PIPE>
 __device__ __forceinline__ void affine_nets_split(const float* __restrict__ S, const AffineSplit& SL,
                                                   const float* __restrict__ Pg, const AffineLayout& L,
-                                                  const float (&xb)[2][(D + 1) / 2], float (&sv)[D], float (&bv)[D]) {
+                                                  const float (&xb)[2][(D + 1) / 2], float (&sv)[D], float (&bv)[D],
+                                                  bool live = false, uint32_t live_idx = 0) {
     constexpr int KS1 = (D + 1) / 2;
     const bool wok = S[SL.ok] != 0.f;
     const float xs = S[SL.ok + 1];
@@ -560,7 +620,17 @@ __device__ __forceinline__ void affine_nets_split(const float* __restrict__ S, c
         fast[st] = wok && __builtin_amdgcn_ballot_w64(bad) == 0;
     }
     if constexpr (PIPE) {
-        affine_nets_split_pipe<HT, D, TILES>(S, SL, xb, sv, bv);
+        bool full = !live;
+        if (live) {
+            affine_nets_split_pipe<HT, D, TILES, true>(S, SL, xb, sv, bv, live_idx);
+            // a zero log-det (see above): every term of some lane may be +-0. (1 - m) * s is zero only
+            // for s = 0 or by underflow, and |1 - m| >= 2^-24 for every m != 1, so |s| < 1e-30 covers it
+            bool zero = true;
+#pragma unroll
+            for (int j = 0; j < D; ++j) zero = zero && fabsf(sv[j]) < 1e-30f;
+            full = __builtin_amdgcn_ballot_w64(zero) != 0;
+        }
+        if (full) affine_nets_split_pipe<HT, D, TILES, false>(S, SL, xb, sv, bv, 0u);
     } else {
         affine_net_split<HT, D, TILES>(S, SL, xb, sv);
         __builtin_amdgcn_sched_barrier(0);  // one net's activations live at a time
@@ -611,7 +681,6 @@ __global__ __launch_bounds__(256) void affine_coupling_kernel(
     for (int j = 0; j < D; ++j) mk[j] = sm[MASK + j];
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) mkb[ks] = (2 * ks + h < D) ? sm[MASK + 2 * ks + h] : 0.f;
-
     // Work split: every wave takes F = nchunks / nwaves whole 64-sample chunks (grid-stride); the
     // R leftover chunks go out as 2R 32-sample half chunks, one to each of the first 2R waves
     // (when 2R <= nwaves), so a SIMD's last round is half a chunk instead of a whole one: at

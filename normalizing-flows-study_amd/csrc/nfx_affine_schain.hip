@@ -15,8 +15,9 @@
 // traffic is the rows in and out once per chain (8d + 8 bytes per sample for the whole chain).
 //
 // Work split: workgroup b owns chunks [b*C/G, (b+1)*C/G) of the C 64-sample chunks, processed in
-// slices that fit its LDS; within a slice wave w takes chunks w, w+NW, ... and leftover chunks
-// go out as 32-sample half chunks when that balances the SIMDs better (as the per-layer kernel).
+// slices that fit its LDS; within a slice wave w takes chunks w, w+NW, ... and the leftover chunks
+// go out as whole chunks and 32-sample half chunks so that the four SIMDs, which meet a barrier
+// every layer, carry equal loads to within a half chunk (chain_share, nfx_chain.h).
 // A sample is always processed by the same lane of the same wave, so layer l+1 reads only what
 // that lane wrote in layer l: the per-layer barrier is needed for the weight buffer alone.
 #include "nfx_chain.h"
@@ -71,11 +72,8 @@ __global__ __launch_bounds__(64 * NW) void affine_schain_kernel(
         for (int e = threadIdx.x; e < rows * D; e += NT) sx[e] = in[r0 * D + e];
         for (int e = threadIdx.x; e < rows; e += NT) sld[e] = accumulate ? logdet[r0 + e] : 0.f;
         const int nch = (int)(s1 - s0);
-        const int F = nch / NW, R = nch - F * NW;
-        const bool split = 2 * R <= NW;
-        const int nfull = split ? F : F + (wave < R ? 1 : 0);
-        const bool half = split && wave < 2 * R;
-        const int half_base = F * NW * 64 + wave * 32;
+        const ChainShare share = chain_share(nch, NW, wave);
+        const int nwhole = share.nfull + (share.xtiles == 2 ? 1 : 0);
 
         for (int li = 0; li < nl; ++li) {
             lds_dma_wait();   // this wave's DMA pieces (and the slice loads) have landed
@@ -92,6 +90,9 @@ __global__ __launch_bounds__(64 * NW) void affine_schain_kernel(
             for (int j = 0; j < D; ++j) mk[j] = W[SL.mask + j];
 #pragma unroll
             for (int ks = 0; ks < KS1; ++ks) mkb[ks] = (2 * ks + h < D) ? W[SL.mask + 2 * ks + h] : 0.f;
+            // the layer's live outputs (the tail's ok[2], ok[3]): may a unit skip the dead ones' fold
+            [[maybe_unused]] const bool elide = (__builtin_amdgcn_readfirstlane(__float_as_uint(W[SL.ok + 2])) & kAffineLiveElide) != 0;
+            [[maybe_unused]] const uint32_t live_idx = __builtin_amdgcn_readfirstlane(__float_as_uint(W[SL.ok + 3]));
 
             auto unit = [&](auto tiles_c, int ub) {
                 constexpr int TILES = decltype(tiles_c)::value;
@@ -124,7 +125,12 @@ __global__ __launch_bounds__(64 * NW) void affine_schain_kernel(
                 }
                 const float* Wi = W + opaque_zero();
                 float sv[D], bv[D];
-                affine_nets_split<HT, D, TILES, affine_split_piped(HT, D)>(Wi, SL, Pg, L, xb, sv, bv);
+                if constexpr (affine_split_piped(HT, D)) {  // (in the straight nets the live fold cost registers: DESIGN.md)
+                    const bool live = elide && affine_live_unit<KS1>(xb, mkb);
+                    affine_nets_split<HT, D, TILES, true>(Wi, SL, Pg, L, xb, sv, bv, live, live_idx);
+                } else {
+                    affine_nets_split<HT, D, TILES, false>(Wi, SL, Pg, L, xb, sv, bv);
+                }
                 if (act) {
 #pragma clang fp contract(off)  // separate mul/add roundings, as affine_coupling_kernel / the reference
                     float y[D];
@@ -149,8 +155,9 @@ __global__ __launch_bounds__(64 * NW) void affine_schain_kernel(
                     sld[so] = first ? ld : sld[so] + ld;
                 }
             };
-            for (int u = 0; u < nfull; ++u) unit(std::integral_constant<int, 2>{}, (wave + u * NW) * 64);
-            if (half) unit(std::integral_constant<int, 1>{}, half_base);
+            for (int u = 0; u < nwhole; ++u)
+                unit(std::integral_constant<int, 2>{}, u < share.nfull ? (wave + u * NW) * 64 : share.xbase);
+            if (share.xtiles == 1) unit(std::integral_constant<int, 1>{}, share.xbase);
             ++g;
         }
         __syncthreads();  // rows of every wave final

@@ -81,11 +81,8 @@ __global__ __launch_bounds__(64 * NW) void spline_schain_kernel(
         }
         for (int e = threadIdx.x; e < rows; e += NTH) sld[e] = accumulate ? logdet[r0 + e] : 0.f;
         const int nch = (int)(s1 - s0);
-        const int F = nch / NW, R = nch - F * NW;
-        const bool split = 2 * R <= NW;
-        const int nfull = split ? F : F + (wave < R ? 1 : 0);
-        const bool half = split && wave < 2 * R;
-        const int half_base = F * NW * 64 + wave * 32;
+        const ChainShare share = chain_share(nch, NW, wave);  // leftovers balanced over the SIMDs
+        const int nwhole = share.nfull + (share.xtiles == 2 ? 1 : 0);
 
         NFX_CMARK(4);  // slice prologue
         for (int li = 0; li < nl; ++li) {
@@ -158,8 +155,9 @@ __global__ __launch_bounds__(64 * NW) void spline_schain_kernel(
                     sld[so] = first ? ld : sld[so] + ld;
                 }
             };
-            for (int u = 0; u < nfull; ++u) unit(std::integral_constant<int, 2>{}, (wave + u * NW) * 64);
-            if (half) unit(std::integral_constant<int, 1>{}, half_base);
+            for (int u = 0; u < nwhole; ++u)
+                unit(std::integral_constant<int, 2>{}, u < share.nfull ? (wave + u * NW) * 64 : share.xbase);
+            if (share.xtiles == 1) unit(std::integral_constant<int, 1>{}, share.xbase);
             ++g;
         }
         NFX_CMARK(3);
