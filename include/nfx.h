@@ -720,6 +720,41 @@ int nfx_cnf_backward(const float* packed, const float* w1, const float* w2, cons
                      float* gw2, float* gb2, float* gw3, float* gb3, float* workspace, int64_t B, int d, int H,
                      float t_begin, float t_end, float step_size, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ResidualFlow (src/flows/advanced/residual_flow.py): x = z + f(z),
+ *   f(z) = W3 act(W2 act(W1 z + b1) + b2) + b3
+ * with every weight spectrally normalised, and the log-det as the truncated Neumann series
+ *   sum_{k=1..neumann_terms} (-1)^(k+1) tr(J^k) / k,   J = df/dz = W3 D2 W2 D1 W1 (d x d, exact).
+ * w1 [H, d], b1 [H], w2 [H, H], b2 [H], w3 [d, H], b3 [d]: the nn.Linear tensors, row-major; u_l,
+ * v_l: the SpectralNorm buffers of layer l (rows, columns of w_l); c_l: its lipschitz_constant.
+ *   nfx_residual_pack   per layer, on the device, one power iteration with the reference's formulas
+ *                       (v <- normalize(W^T u), u <- normalize(W v), eps 1e-12, sigma = u . W v), then
+ *                       W_eff = W * ((1 / sigma) * c) where sigma > c, else W; writes the image of the
+ *                       effective weights, nfx_residual_packed_floats floats. Nothing is read back to
+ *                       the host and u, v are not written (eval-mode semantics).
+ *   nfx_residual_flow   direction NFX_FORWARD: out = in + f(in), log_det = +Neumann sum at in.
+ *                       NFX_INVERSE: z <- x - f(z) from z = x, at most max_iter times; a sample
+ *                       stops when its OWN ||z_new - z||_2 < tol and keeps z, the iterate before that
+ *                       step (one that reaches max_iter keeps its last z_new); out = z, log_det =
+ *                       -Neumann sum at z. A row's result does not depend on the other rows.
+ * No guards and no clamps (the reference has none). activation: NFX_RESIDUAL_*. Kernel family:
+ * 1 <= d <= 8, 1 <= H <= 128 (the image pads H to 32, 64 or 128), any B >= 1
+ * (nfx_residual_supported: 1 inside it, host-only check); NFX_EUNSUPPORTED elsewhere. B == 0 is a
+ * no-op. accumulate adds the log-det into log_det. in and out must not alias.
+ * ------------------------------------------------------------------------------------- */
+#define NFX_RESIDUAL_RELU 0
+#define NFX_RESIDUAL_ELU 1
+#define NFX_RESIDUAL_LEAKY_RELU 2 /* negative slope 0.1 */
+#define NFX_RESIDUAL_TANH 3
+size_t nfx_residual_packed_floats(int d, int H);
+int nfx_residual_supported(int64_t B, int d, int H, int activation);
+int nfx_residual_pack(const float* w1, const float* b1, const float* u1, const float* v1, float c1, const float* w2,
+                      const float* b2, const float* u2, const float* v2, float c2, const float* w3, const float* b3,
+                      const float* u3, const float* v3, float c3, int d, int H, float* packed, void* stream);
+int nfx_residual_flow(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d, int H,
+                      int activation, int direction, int neumann_terms, int max_iter, float tol, int accumulate,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

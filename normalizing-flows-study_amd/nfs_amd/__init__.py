@@ -6,12 +6,13 @@ src/models/*), backed by hand-written HIP kernels in libnfx.so (C-ABI: include/n
 from . import _lib
 from .flows import (Flow, SequentialFlow, CouplingLayer, SplineCouplingLayer,
                     rational_quadratic_spline, ARQS, MaskedLinear, MADE, MaskedAutoregressiveFlow,
-                    InverseAutoregressiveFlow, made_degrees, ODEFunc, ContinuousFlow, STATS,
-                    reset_stats)
+                    InverseAutoregressiveFlow, made_degrees, ODEFunc, ContinuousFlow, SpectralNorm, ResidualBlock,
+                    ResidualFlow, STATS, reset_stats)
 from .models import NormalizingFlowModel, RealNVP, RealNVPSpline, gauss_logprob
 from .graphs import GraphedFlow, GraphedTrainStep
 
 __all__ = ["Flow", "SequentialFlow", "CouplingLayer", "SplineCouplingLayer",
            "rational_quadratic_spline", "ARQS", "MaskedLinear", "MADE", "MaskedAutoregressiveFlow",
-           "InverseAutoregressiveFlow", "ODEFunc", "ContinuousFlow", "NormalizingFlowModel", "RealNVP", "RealNVPSpline",
+           "InverseAutoregressiveFlow", "ODEFunc", "ContinuousFlow", "SpectralNorm", "ResidualBlock",
+           "ResidualFlow", "NormalizingFlowModel", "RealNVP", "RealNVPSpline",
            "gauss_logprob", "made_degrees", "STATS", "reset_stats", "GraphedFlow", "GraphedTrainStep"]

@@ -32,6 +32,10 @@ NFX_MADE_SEQ_AUTO = 0
 NFX_MADE_SEQ_SEGMENT = 1
 NFX_MADE_SEQ_WAVE = 2
 NFX_MADE_SEQ_PUSH = 3
+NFX_RESIDUAL_RELU = 0
+NFX_RESIDUAL_ELU = 1
+NFX_RESIDUAL_LEAKY_RELU = 2
+NFX_RESIDUAL_TANH = 3
 
 
 class NfxLibraryError(RuntimeError):
@@ -140,6 +144,10 @@ _SIGNATURES = {
     "nfx_cnf_pack_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
     "nfx_cnf_integrate_save": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _f, _f, _f, _int, _vp]),
     "nfx_cnf_backward": (_int, [_vp] * 16 + [_i64, _int, _int, _f, _f, _f, _vp]),
+    "nfx_residual_packed_floats": (_sz, [_int, _int]),
+    "nfx_residual_supported": (_int, [_i64, _int, _int, _int]),
+    "nfx_residual_pack": (_int, [_vp, _vp, _vp, _vp, _f] * 3 + [_int, _int, _vp, _vp]),
+    "nfx_residual_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _f, _int, _vp]),
     "nfx_rqs_unit": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int,
                                      _vp]),
@@ -210,7 +218,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
     "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
-    "nfx_made_sample_supported"))
+    "nfx_made_sample_supported", "nfx_residual_supported"))
 
 
 _as_pointer = _vp.from_param  # (an int as a full-width pointer argument, without a c_void_p object)

@@ -1,0 +1,82 @@
+"""Shared weights, inputs and references of the ResidualFlow tests (test_residual_cpu.py,
+test_gpu_residual.py)."""
+import functools
+
+import torch
+
+import nfs_amd
+
+ACTIVATIONS = ("relu", "elu", "leaky_relu", "tanh")
+
+
+def redraw(flow, seed, weight_scale=1.0):
+    """Redraw every layer of a ResidualFlow-shaped module in place (this project's or the
+    reference's: same submodule names): Xavier-normal weights times `weight_scale`, biases
+    0.1 N(0, 1), and fresh unit `u`, `v`. Gain 1 puts sigma of every layer above c = 0.45 (the
+    normalisation engages); the constructor's gain 0.1 alone never does."""
+    g = torch.Generator().manual_seed(seed)
+    block = flow.residual_block
+    with torch.no_grad():
+        for layer in (block.layer1, block.layer2, block.layer3):
+            lin = layer.module
+            fan_out, fan_in = lin.weight.shape
+            lin.weight.copy_(torch.randn(lin.weight.shape, generator=g) * weight_scale * (2.0 / (fan_in + fan_out)) ** 0.5)
+            lin.bias.copy_(0.1 * torch.randn(lin.bias.shape, generator=g))
+            layer.u.copy_(torch.nn.functional.normalize(torch.randn(layer.u.shape, generator=g), dim=0))
+            layer.v.copy_(torch.nn.functional.normalize(torch.randn(layer.v.shape, generator=g), dim=0))
+    return flow
+
+
+def make_flow(d, H, act="relu", lipschitz=0.9, seed=0, weight_scale=1.0, **kw):
+    """ResidualFlow(d, H) in eval mode with every layer redrawn (`redraw`). Fixed seed."""
+    flow = nfs_amd.ResidualFlow(d, H, lipschitz_constant=lipschitz, activation=act, **kw)
+    return redraw(flow, 5200 + 131 * seed + 17 * d + H, weight_scale).eval()
+
+
+def sigmas(flow):
+    """[(sigma, c)] per layer: what one power iteration from the stored (u, v) gives, in float64."""
+    out = []
+    for layer in flow.residual_block.layers():
+        w, u = layer.module.weight.detach().double(), layer.u.double()
+        v = torch.nn.functional.normalize(w.t() @ u, dim=0)
+        u = torch.nn.functional.normalize(w @ v, dim=0)
+        out.append((float(u @ (w @ v)), float(layer.lipschitz_constant)))
+    return out
+
+
+def make_inputs(B, d, seed=0):
+    """Rows from N(0, 1.5^2)."""
+    g = torch.Generator().manual_seed(1977 + seed)
+    return 1.5 * torch.randn(B, d, generator=g)
+
+
+def as_double(flow):
+    """A float64 copy of `flow` (same weights, buffers, settings and mode)."""
+    block = flow.residual_block
+    act = {"ReLU": "relu", "ELU": "elu", "LeakyReLU": "leaky_relu", "Tanh": "tanh"}[type(block.activation).__name__]
+    f64 = nfs_amd.ResidualFlow(flow.dim, flow.hidden_dim, lipschitz_constant=flow.lipschitz_constant, activation=act,
+                               max_iter=flow.max_iter, tol=flow.tol, neumann_terms=flow.neumann_terms).double()
+    f64.load_state_dict({k: v.double() for k, v in flow.state_dict().items()})
+    return f64.train(flow.training)
+
+
+def composite(flow, x, direction):
+    """The torch composite on the CPU in x's dtype: (y, ld)."""
+    with torch.no_grad():
+        return flow.forward(x) if direction > 0 else flow.inverse(x)
+
+
+B_MAX = 4099
+
+
+@functools.lru_cache(maxsize=None)
+def parity_case(d, H, act, lipschitz, direction):
+    """(flow, x [B_MAX, d], (y32, ld32), (y64, ld64)): the shared-weights flow, its inputs, and the
+    fp32 and float64 CPU composites in `direction`. Rows are independent (the composite's stopping
+    rule is per sample), so a test at a smaller batch slices these; computed once per session and
+    never modified."""
+    flow = make_flow(d, H, act, lipschitz)
+    x = make_inputs(B_MAX, d, seed=3 + (direction > 0))
+    c32 = composite(flow, x, direction)
+    c64 = composite(as_double(flow), x.double(), direction)
+    return flow, x, c32, c64
