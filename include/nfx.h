@@ -755,6 +755,55 @@ int nfx_residual_flow(const float* packed, const float* in, float* out, float* l
                       int activation, int direction, int neumann_terms, int max_iter, float tol, int accumulate,
                       void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * NeuralAutoregressiveFlow (src/flows/advanced/neural_autoregressive_flow.py): an affine
+ * autoregressive flow on the DeepMADE conditioner,
+ *   h_0 = act(LN(W_0 x + b_0)),  h_l = act(LN(W_l h_(l-1) + b_l)) [+ h_(l-1) in a residual block],
+ *   (mu, alpha) = clamp(W_out h_last + b_out, -2, 2),   W = weight * mask everywhere,
+ * with n_hidden hidden layers of widths[0 .. n_hidden) (a HOST array) and LN a LayerNorm over the
+ * layer's width (biased variance, 1 / sqrtf(var + eps)).
+ *   nfx_naf_pack   layers[0 .. n_hidden]: the hidden layers, then the output layer [2 d, widths[last]]
+ *                  (rows 0..d-1 mu, d..2d-1 alpha). Device pointers, row-major; mask NULL = all ones;
+ *                  ln_weight / ln_bias NULL = no LayerNorm on that layer; residual is checked against
+ *                  the widths. Writes nfx_naf_packed_floats floats on the device, reads nothing back.
+ *   nfx_naf_flow   NFX_INVERSE, one conditioner pass: a = clamp(alpha, +-clamp_alpha), s = clamp(-a,
+ *                  +-clamp_log_scale), out = (in - mu) exp(s), log_det = sum s.
+ *                  NFX_FORWARD, d conditioner passes from x = 0, each through the whole network: pass i
+ *                  sets x_i = in_i exp(s_i) + mu_i with s_i = clamp(clamp(alpha_i, +-clamp_alpha),
+ *                  +-clamp_log_scale); log_det = sum s_i. (With LayerNorm the conditioner is not
+ *                  autoregressive, so this is not the inverse of NFX_INVERSE: the reference's behaviour.)
+ *                  Both: NaN / Inf elements of out become 0, a NaN / Inf log_det becomes 0, then
+ *                  log_det is clamped to +-100. A row's result does not depend on the other rows.
+ * flags: NFX_NAF_LAYER_NORM, and NFX_NAF_RESIDUAL(l) for a hidden layer l >= 1 that is a residual
+ * block (widths[l] == widths[l - 1]); they must describe what was packed. activation: NFX_NAF_*.
+ * Kernel family: 1 <= d <= 16, 1 <= n_hidden <= 4, every width in 1..128, and an image (every width
+ * padded to a multiple of 32) within the 160 KiB of LDS of one workgroup; any B >= 1
+ * (nfx_naf_supported: 1 inside it, host-only check; nfx_naf_packed_floats is 0 outside it);
+ * NFX_EUNSUPPORTED elsewhere. B == 0 is a no-op. accumulate adds the log-det into log_det. in and
+ * out must not alias.
+ * ------------------------------------------------------------------------------------- */
+#define NFX_NAF_RELU 0
+#define NFX_NAF_ELU 1
+#define NFX_NAF_LEAKY_RELU 2 /* negative slope 0.1 */
+#define NFX_NAF_GELU 3       /* exact: 0.5 x (1 + erf(x / sqrt 2)) */
+#define NFX_NAF_LAYER_NORM 1
+#define NFX_NAF_RESIDUAL(l) (2 << (l))
+typedef struct NfxNafLayer {
+    const float* weight;    /* [out, in] */
+    const float* bias;      /* [out] */
+    const float* mask;      /* [out, in] of 0 / 1, or NULL */
+    const float* ln_weight; /* [out], or NULL */
+    const float* ln_bias;   /* [out], or NULL */
+    float ln_eps;
+    int residual; /* 1: act(LN(W h + b)) + h */
+} NfxNafLayer;
+size_t nfx_naf_packed_floats(int d, int n_hidden, const int* widths);
+int nfx_naf_supported(int64_t B, int d, int n_hidden, const int* widths, int activation, int flags);
+int nfx_naf_pack(const NfxNafLayer* layers, int d, int n_hidden, const int* widths, float* packed, void* stream);
+int nfx_naf_flow(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d, int n_hidden,
+                 const int* widths, int activation, int flags, float clamp_alpha, float clamp_log_scale,
+                 int direction, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

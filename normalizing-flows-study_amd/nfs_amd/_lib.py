@@ -36,6 +36,16 @@ NFX_RESIDUAL_RELU = 0
 NFX_RESIDUAL_ELU = 1
 NFX_RESIDUAL_LEAKY_RELU = 2
 NFX_RESIDUAL_TANH = 3
+NFX_NAF_RELU = 0
+NFX_NAF_ELU = 1
+NFX_NAF_LEAKY_RELU = 2
+NFX_NAF_GELU = 3
+NFX_NAF_LAYER_NORM = 1
+
+
+def NFX_NAF_RESIDUAL(l):
+    """The nfx_naf_flow flag of hidden layer l being a residual block."""
+    return 2 << l
 
 
 class NfxLibraryError(RuntimeError):
@@ -58,6 +68,19 @@ class NfxMlpRaw(ctypes.Structure):
         ("bn_rv", ctypes.c_void_p * 3),
         ("bn_eps", ctypes.c_float),
         ("n_layers", ctypes.c_int),
+    ]
+
+
+class NfxNafLayer(ctypes.Structure):
+    """Mirror of `NfxNafLayer` in include/nfx.h (device pointers of one DeepMADE layer)."""
+    _fields_ = [
+        ("weight", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p),
+        ("mask", ctypes.c_void_p),
+        ("ln_weight", ctypes.c_void_p),
+        ("ln_bias", ctypes.c_void_p),
+        ("ln_eps", ctypes.c_float),
+        ("residual", ctypes.c_int),
     ]
 
 
@@ -148,6 +171,10 @@ _SIGNATURES = {
     "nfx_residual_supported": (_int, [_i64, _int, _int, _int]),
     "nfx_residual_pack": (_int, [_vp, _vp, _vp, _vp, _f] * 3 + [_int, _int, _vp, _vp]),
     "nfx_residual_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _f, _int, _vp]),
+    "nfx_naf_packed_floats": (_sz, [_int, _int, _vp]),
+    "nfx_naf_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
+    "nfx_naf_pack": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+    "nfx_naf_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _f, _f, _int, _int, _vp]),
     "nfx_rqs_unit": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int,
                                      _vp]),
@@ -218,7 +245,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
     "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
-    "nfx_made_sample_supported", "nfx_residual_supported"))
+    "nfx_made_sample_supported", "nfx_residual_supported", "nfx_naf_supported"))
 
 
 _as_pointer = _vp.from_param  # (an int as a full-width pointer argument, without a c_void_p object)

@@ -7,9 +7,10 @@ from .autoregressive import (MaskedLinear, MADE, MaskedAutoregressiveFlow,
                              InverseAutoregressiveFlow, made_degrees)
 from .continuous import ODEFunc, ContinuousFlow
 from .residual import SpectralNorm, ResidualBlock, ResidualFlow
+from .naf import DeepMADE, NeuralAutoregressiveFlow
 
 __all__ = ["Flow", "SequentialFlow", "HipFlow", "CouplingLayer", "SplineCouplingLayer",
            "rational_quadratic_spline", "ARQS", "MaskedLinear", "MADE", "MaskedAutoregressiveFlow",
            "InverseAutoregressiveFlow", "made_degrees", "ODEFunc", "ContinuousFlow", "SpectralNorm", "ResidualBlock",
-           "ResidualFlow", "STATS", "reset_stats", "drop_pack_caches",
+           "ResidualFlow", "DeepMADE", "NeuralAutoregressiveFlow", "STATS", "reset_stats", "drop_pack_caches",
            "drop_layer_pack_caches"]
