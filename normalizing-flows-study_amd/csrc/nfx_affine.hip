@@ -334,29 +334,6 @@ static int affine_launch(const float* packed, const float* in, float* out, float
     return check_launch("affine_coupling_kernel");
 }
 
-// Grid: enough resident workgroups to fill every CU (occupancy from the runtime), never more
-// than there are 4-chunk groups of work.
-int resident_grid(const void* kernel, int threads, size_t lds_bytes, int64_t work_groups) {
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, lds_bytes) != hipSuccess ||
-        per_cu <= 0)
-        per_cu = 1;
-    int64_t g = (int64_t)num_cus() * per_cu;
-    if (work_groups < g) g = work_groups;
-    return (int)(g < 1 ? 1 : g);
-}
-
-int prepare_lds(const void* kernel, size_t bytes) {
-    if (bytes > 65536) {
-        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) !=
-            hipSuccess) {
-            (void)hipGetLastError();  // do not leave the error sticky for the caller's next HIP call
-            return set_error(NFX_ELAUNCH, "hipFuncSetAttribute(dynamic LDS %zu B) failed", bytes);
-        }
-    }
-    return NFX_OK;
-}
-
 }  // namespace nfx
 
 using namespace nfx;

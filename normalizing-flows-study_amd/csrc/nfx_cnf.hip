@@ -26,24 +26,10 @@
 
 namespace nfx {
 
-template <>
-cnf_kernel_t cnf_pick_ht<1>(int d);
-template <>
-cnf_kernel_t cnf_pick_ht<2>(int d);
-template <>
-cnf_kernel_t cnf_pick_ht<4>(int d);
-template <>
-cnf_kernel_t cnf_save_pick_ht<1>(int d);
-template <>
-cnf_kernel_t cnf_save_pick_ht<2>(int d);
-
-static cnf_kernel_t pick_cnf(int d, int H) {
-    switch (H) {
-        case 32: return cnf_pick_ht<1>(d);
-        case 64: return cnf_pick_ht<2>(d);
-        case 128: return cnf_pick_ht<4>(d);
-        default: return nullptr;
-    }
+static cnf_kernel_t pick_cnf(bool save, int d, int H) {
+    if (H % 32) return nullptr;
+    if (save) return pick_of<1, 2>(H / 32, [&](auto HT) -> cnf_kernel_t { return cnf_save_pick_ht<HT()>(d); });
+    return pick_of<1, 2, 4>(H / 32, [&](auto HT) -> cnf_kernel_t { return cnf_pick_ht<HT()>(d); });
 }
 
 static bool cnf_family(int d, int H) { return d >= 1 && d <= kCnfMaxD && (H == 32 || H == 64 || H == 128); }
@@ -65,15 +51,15 @@ __global__ void cnf_pack_kernel(const float* __restrict__ w1, const float* __res
             const int row = acc_vec_row(t);
             v = second ? b2[row] : b1[row];
         } else if (o < L.b3) {  // w3: row j of W3
-            const int t = o - L.w3, j = t / H;
-            v = w3[j * H + acc_vec_row(t % H)];
+            const VecRow e = acc_rows_elem(o - L.w3, HT);
+            v = w3[e.vec * H + e.row];
         } else if (o < L.c2) {  // b3
             const int j = o - L.b3;
             v = j < d ? b3[j] : 0.f;
         } else {  // c2, w2: A operands over (out row k, hidden input j)
             const bool trace = o < L.w2;
-            const ATileElem e = a_tile_elem(o - (trace ? L.c2 : L.w2));
-            const int k = 32 * (e.tile / HT) + e.row, j = 32 * (e.tile % HT) + e.k;
+            const RowCol e = a_image_elem(o - (trace ? L.c2 : L.w2), HT);
+            const int k = e.row, j = e.col;
             v = w2[k * H + j];
             if (trace) {  // C[k, j] = W2[k, j] * sum_i W3[i, k] W1[j, i]
                 double n = 0.0;
@@ -101,7 +87,7 @@ extern "C" int nfx_cnf_pack(const float* w1, const float* b1, const float* w2, c
     if (d <= 0 || H <= 0) return set_error(NFX_EINVAL, "cnf_pack: bad shape d=%d H=%d", d, H);
     if (!cnf_family(d, H))
         return set_error(NFX_EUNSUPPORTED, "cnf: d=%d H=%d outside the compiled family (d<=8, H in {32,64,128})", d, H);
-    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !packed) return set_error(NFX_EINVAL, "cnf_pack: null pointer");
+    if (int rc = check_pointers("cnf_pack", {w1, b1, w2, b2, w3, b3, packed})) return rc;
     const int total = (int)nfx_cnf_packed_floats(d, H);
     cnf_pack_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(w1, b1, w2, b2, w3, b3, d, H, packed);
     return check_launch("cnf_pack_kernel");
@@ -114,17 +100,17 @@ static int cnf_launch(bool save, const float* packed, const float* in, float* ou
     if (B < 0 || d <= 0 || H <= 0) return set_error(NFX_EINVAL, "cnf: bad shape B=%lld d=%d H=%d", (long long)B, d, H);
     if (!(step_size > 0.f) || !isfinite(step_size) || !isfinite(t_begin) || !isfinite(t_end))
         return set_error(NFX_EINVAL, "cnf: times must be finite and step_size positive");
-    cnf_kernel_t k = save ? (H == 32 ? cnf_save_pick_ht<1>(d) : H == 64 ? cnf_save_pick_ht<2>(d) : nullptr)
-                          : pick_cnf(d, H);
+    cnf_kernel_t k = pick_cnf(save, d, H);
     if (!k)
         return set_error(NFX_EUNSUPPORTED, "cnf: d=%d H=%d outside the compiled family (d<=8, H in %s)", d, H,
                          save ? "{32,64}" : "{32,64,128}");
     CnfArgs A{};
-    if (!cnf_grid(t_begin, t_end, step_size, A)) return set_error(NFX_EINVAL, "cnf: too many steps");
+    if (!cnf_grid(t_begin, t_end, step_size, A.g)) return set_error(NFX_EINVAL, "cnf: too many steps");
     if (B == 0) return NFX_OK;
-    if (!packed || !in || !out || !log_det || (save && A.nsteps > 0 && !traj))
-        return set_error(NFX_EINVAL, "cnf: null pointer");
-    if (in == out) return set_error(NFX_EINVAL, "cnf: in and out must not alias");
+    if (int rc = check_pointers("cnf", {packed, in, out, log_det})) return rc;
+    if (save && A.g.nsteps > 0)
+        if (int rc = check_pointers("cnf", {traj})) return rc;
+    if (int rc = check_no_alias("cnf", in, out)) return rc;
     A.packed = packed;
     A.in = in;
     A.out = out;
@@ -135,15 +121,9 @@ static int cnf_launch(bool save, const float* packed, const float* in, float* ou
     A.accumulate = accumulate ? 1 : 0;
     const CnfLayout L = cnf_layout(d, H / 32);
     const size_t lds = (size_t)(H <= 64 ? L.w2 : L.total) * sizeof(float);
-    // Few tiles: one wave per workgroup, so they spread over every CU; many: four waves share one
-    // staged weight image.
-    const int threads = A.ntiles >= (int64_t)8 * num_cus() ? 256 : 64;
-    const int nw = threads / 64;
-    int rc = prepare_lds((const void*)k, lds);
-    if (rc) return rc;
-    const int grid = resident_grid((const void*)k, threads, lds, (A.ntiles + nw - 1) / nw);
-    k<<<grid, threads, lds, (hipStream_t)stream>>>(A);
-    return check_launch(save ? "cnf_save_kernel" : "cnf_kernel");
+    const int threads = tile_owner_threads(A.ntiles), nw = threads / 64;
+    return launch_resident((const void*)k, &A, threads, lds, (A.ntiles + nw - 1) / nw, (hipStream_t)stream,
+                           save ? "cnf_save_kernel" : "cnf_kernel");
 }
 
 extern "C" int nfx_cnf_integrate(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,
@@ -159,9 +139,9 @@ extern "C" int nfx_cnf_integrate_save(const float* packed, const float* in, floa
 }
 
 extern "C" size_t nfx_cnf_trajectory_floats(int64_t B, int d, float t_begin, float t_end, float step_size) {
-    CnfArgs A{};
+    CnfGrid G{};
     if (B <= 0 || d <= 0 || !(step_size > 0.f) || !isfinite(step_size) || !isfinite(t_begin) || !isfinite(t_end) ||
-        !cnf_grid(t_begin, t_end, step_size, A))
+        !cnf_grid(t_begin, t_end, step_size, G))
         return 0;
-    return cnf_traj_floats(B, d, A.nsteps);
+    return cnf_traj_floats(B, d, G.nsteps);
 }

@@ -42,16 +42,11 @@
 
 namespace nfx {
 
-template <>
-cnf_bwd_kernel_t cnf_bwd_pick_ht<1>(int d);
-template <>
-cnf_bwd_kernel_t cnf_bwd_pick_ht<2>(int d);
-
 static bool cnf_bwd_family(int d, int H) { return d >= 1 && d <= kCnfMaxD && (H == 32 || H == 64); }
 
 static cnf_bwd_kernel_t pick_cnf_bwd(int d, int H) {
     if (!cnf_bwd_family(d, H)) return nullptr;
-    return H == 32 ? cnf_bwd_pick_ht<1>(d) : cnf_bwd_pick_ht<2>(d);
+    return pick_of<1, 2>(H / 32, [&](auto HT) -> cnf_bwd_kernel_t { return cnf_bwd_pick_ht<HT()>(d); });
 }
 
 // The part of the backward image behind the forward image (which nfx_cnf_pack writes).
@@ -63,8 +58,8 @@ __global__ void cnf_bwd_pack_kernel(const float* __restrict__ w1, const float* _
         float v = 0.f;
         if (o < L.w1c) {  // c2t, w2t: A operands over (out row j, contraction index k) of M^T
             const bool trace = o < L.w2t;
-            const ATileElem e = a_tile_elem(o - (trace ? L.c2t : L.w2t));
-            const int j = 32 * (e.tile / HT) + e.row, k = 32 * (e.tile % HT) + e.k;
+            const RowCol e = a_image_elem(o - (trace ? L.c2t : L.w2t), HT);
+            const int j = e.row, k = e.col;
             v = w2[k * H + j];
             if (trace) {  // C[k, j], rounded as the forward pack rounds it
                 double n = 0.0;
@@ -72,8 +67,8 @@ __global__ void cnf_bwd_pack_kernel(const float* __restrict__ w1, const float* _
                 v = (float)((double)v * n);
             }
         } else if (o < L.w1c + d * HT * 32) {  // w1c: column i of W1
-            const int t = o - L.w1c, i = t / H;
-            v = w1[acc_vec_row(t % H) * (d + 1) + i];
+            const VecRow e = acc_rows_elem(o - L.w1c, HT);
+            v = w1[e.row * (d + 1) + e.vec];
         }
         packed[o] = v;
     }
@@ -168,9 +163,9 @@ extern "C" int nfx_cnf_pack_backward(const float* w1, const float* b1, const flo
     if (!cnf_bwd_family(d, H))
         return set_error(NFX_EUNSUPPORTED, "cnf backward: d=%d H=%d outside the compiled family (d<=8, H in {32,64})", d,
                          H);
-    if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !packed)
-        return set_error(NFX_EINVAL, "cnf_pack_backward: null pointer");
-    int rc = nfx_cnf_pack(w1, b1, w2, b2, w3, b3, d, H, packed, stream);
+    int rc = check_pointers("cnf_pack_backward", {w1, b1, w2, b2, w3, b3, packed});
+    if (rc) return rc;
+    rc = nfx_cnf_pack(w1, b1, w2, b2, w3, b3, d, H, packed, stream);
     if (rc) return rc;
     const CnfBwdLayout L = cnf_bwd_layout(d, H / 32);
     cnf_bwd_pack_kernel<<<(L.total - L.c2t + 255) / 256, 256, 0, (hipStream_t)stream>>>(w1, w2, w3, d, H, packed);
@@ -190,11 +185,11 @@ extern "C" int nfx_cnf_backward(const float* packed, const float* w1, const floa
     if (!k)
         return set_error(NFX_EUNSUPPORTED, "cnf backward: d=%d H=%d outside the compiled family (d<=8, H in {32,64})", d,
                          H);
-    CnfArgs G{};
+    CnfGrid G{};
     if (!cnf_grid(t_begin, t_end, step_size, G)) return set_error(NFX_EINVAL, "cnf backward: too many steps");
     if (B == 0) return NFX_OK;
-    if (!gy || !gx || !gw1 || !gb1 || !gw2 || !gb2 || !gw3 || !gb3)
-        return set_error(NFX_EINVAL, "cnf backward: null pointer");
+    int rc = check_pointers("cnf backward", {gy, gx, gw1, gb1, gw2, gb2, gw3, gb3});
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (G.nsteps == 0) {  // equal times: the identity, no parameter takes part
         if (gx != gy && hipMemcpyAsync(gx, gy, sizeof(float) * (size_t)B * d, hipMemcpyDeviceToDevice, s) != hipSuccess)
@@ -206,8 +201,8 @@ extern "C" int nfx_cnf_backward(const float* packed, const float* w1, const floa
                 return set_error(NFX_ELAUNCH, "cnf backward: memset failed");
         return NFX_OK;
     }
-    if (!packed || !w1 || !w2 || !w3 || !in || !traj || !gld || !workspace)
-        return set_error(NFX_EINVAL, "cnf backward: null pointer");
+    rc = check_pointers("cnf backward", {packed, w1, w2, w3, in, traj, gld, workspace});
+    if (rc) return rc;
     if (gx == gy || gx == in) return set_error(NFX_EINVAL, "cnf backward: gx must not alias gy or in");
     CnfBwdArgs A{};
     A.packed = packed;
@@ -219,15 +214,11 @@ extern "C" int nfx_cnf_backward(const float* packed, const float* w1, const floa
     A.ws = workspace;
     A.B = B;
     A.ntiles = (B + 31) / 32;
-    A.nsteps = G.nsteps;
-    A.s0 = G.s0;
-    A.s1 = G.s1;
-    A.h = G.h;
-    A.sgn = G.sgn;
+    A.g = G;
     const int HT = H / 32;
     const int threads = cnf_bwd_threads(A.ntiles), nw = threads / 64, grid = cnf_bwd_grid(A.ntiles);
     const size_t lds = sizeof(float) * ((size_t)cnf_bwd_layout(d, HT).total + (size_t)nw * cnf_bwd_wave_floats(HT));
-    int rc = prepare_lds((const void*)k, lds);
+    rc = prepare_lds((const void*)k, lds);
     if (rc) return rc;
     k<<<grid, threads, lds, s>>>(A);
     rc = check_launch("cnf_bwd_kernel");

@@ -85,8 +85,7 @@ struct CnfBwdArgs {
     float* gx;           // [B][d]
     float* ws;           // [grid * waves][CnfBwdPartial::total]
     int64_t B, ntiles;
-    int nsteps;          // >= 1 (equal times never launch)
-    float s0, s1, h, sgn;
+    CnfGrid g;           // nsteps >= 1 (equal times never launch)
 };
 
 template <int HT, int D>
@@ -94,14 +93,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr CnfBwdLayout L = cnf_bwd_layout(D, HT);
     constexpr CnfLayout F = L.F;
     constexpr CnfBwdPartial P = cnf_bwd_partial(D, HT);
-    constexpr int KS1 = F.KS1;
     constexpr int PITCH = kCnfBwdPitch;
     extern __shared__ f32x4 lds4[];
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(A.packed);
-        for (int i = threadIdx.x; i < L.total / 4; i += blockDim.x) lds4[i] = src[i];
-    }
-    __syncthreads();
+    stage_image(lds4, A.packed, L.total / 4);
     float* sm = reinterpret_cast<float*>(lds4);
 
     const int lane = lane_id(), h = lane >> 5, col = lane & 31;
@@ -157,14 +151,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         return XT;
     };
 
-    // One evaluation of the field at (t, z). vjp == false: out = v, tr = the divergence (as
-    // cnf_kernel's field). vjp == true: the cotangents (vb, cl * l_bar) of (v, tr) are pulled back:
-    // out = z_bar, and the evaluation's share of every parameter gradient joins the accumulators.
+    // One evaluation of the field at (t, z), the arithmetic of cnf_kernel's field with every h2 tile
+    // and its trace companion q = C g1 kept. vjp == false: out = v, tr = the divergence. vjp == true:
+    // the cotangents (vb, cl * l_bar) of (v, tr) are pulled back: out = z_bar, and the evaluation's
+    // share of every parameter gradient joins the accumulators.
     float lbar = 0.f;  // l_bar of sample col (ls holds it by sample for the transposed layout)
     auto stage = [&](float t, const float (&z)[D], bool vjp, const float (&vb)[D], float cl, float (&out)[D],
                      float& tr) {
         const int oz = opaque_zero();  // no hoisting of the LDS operands out of the step loop
         const float* s = sm + oz;
+        constexpr int KS1 = F.KS1;
         float xb[KS1];
 #pragma unroll
         for (int ks = 0; ks < KS1; ++ks) {
@@ -217,11 +213,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int j = 0; j < D; ++j) {
                 float pv = 0.f;
 #pragma unroll
-                for (int ht = 0; ht < HT; ++ht) {
-                    const f32x16 w3 = load_bias16(s + F.w3 + (j * HT + ht) * 32, h);
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) pv = fmaf(w3[r], h2[ht][r], pv);
-                }
+                for (int ht = 0; ht < HT; ++ht) pv = acc_dot16(s + F.w3 + (j * HT + ht) * 32, h, h2[ht], pv);
                 out[j] = halves_sum(pv, pv) + s[F.b3 + j];
             }
             tr = halves_sum(ptr, ptr);
@@ -327,11 +319,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         for (int j = 0; j < D; ++j) {
             float pz = 0.f;
 #pragma unroll
-            for (int ht = 0; ht < HT; ++ht) {
-                const f32x16 w = load_bias16(s + L.w1c + (j * HT + ht) * 32, h);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pz = fmaf(w[r], a1[ht][r], pz);
-            }
+            for (int ht = 0; ht < HT; ++ht) pz = acc_dot16(s + L.w1c + (j * HT + ht) * 32, h, a1[ht], pz);
             out[j] = halves_sum(pz, pz);
             ab3[j] += vb[j];
         }
@@ -358,13 +346,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // dead column: zero state and zero cotangents, so it adds exact zeros to every sum.
         bool dead = !live;
         float ybar[D];
-        const float* yfin = A.traj + ((int64_t)(A.nsteps - 1) * A.B + srow) * D;
+        const float* yfin = A.traj + ((int64_t)(A.g.nsteps - 1) * A.B + srow) * D;
 #pragma unroll
         for (int j = 0; j < D; ++j) {
             ybar[j] = live ? yfin[j] : 0.f;  // (the unclamped y_n for now)
             dead = dead || nonfinite(live ? A.x[srow * D + j] : 0.f) || nonfinite(ybar[j]);
         }
-        const float ldfin = live ? A.traj[(int64_t)A.nsteps * A.B * D + srow] : 0.f;
+        const float ldfin = live ? A.traj[(int64_t)A.g.nsteps * A.B * D + srow] : 0.f;
         // torch.clamp passes the gradient where the input lies in [-10, 10], bounds included
 #pragma unroll
         for (int j = 0; j < D; ++j)
@@ -375,12 +363,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         wave_lds_sync();
 
 #pragma unroll 1
-        for (int k = A.nsteps - 1; k >= 0; --k) {
-#pragma clang fp contract(off)  // the stage inputs round as cnf_kernel's
-            const float sk = (float)k * A.h + A.s0;
-            const float sk1 = k + 1 == A.nsteps ? A.s1 : (float)(k + 1) * A.h + A.s0;
-            const float t0 = A.sgn * sk, t1 = A.sgn * sk1;
-            const float dt = t1 - t0;
+        for (int k = A.g.nsteps - 1; k >= 0; --k) {
+#pragma clang fp contract(off)  // the cotangents' mul/adds round separately, as the stage inputs'
+            const CnfStep S = cnf_step(A.g, k);
+            const float dt = S.dt;
             float y[D];
             const float* yk = k == 0 ? A.x + srow * D : A.traj + ((int64_t)(k - 1) * A.B + srow) * D;
 #pragma unroll
@@ -396,30 +382,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #pragma unroll
                 for (int j = 0; j < D; ++j) {
                     if (sg == 1) {
-                        zin[j] = y[j];
+                        zin[j] = cnf_stage_input(1, dt, y[j], 0.f, 0.f, 0.f);
                         vb[j] = dt * 0.125f * ybar[j] + dt * zb4[j] - dt / 3.f * zb3[j] + dt / 3.f * zb2[j];
                     } else if (sg == 2) {
-                        zin[j] = y[j] + dt * k1[j] / 3.f;
+                        zin[j] = cnf_stage_input(2, dt, y[j], k1[j], k2[j], k3[j]);
                         vb[j] = 3.f * dt * 0.125f * ybar[j] - dt * zb4[j] + dt * zb3[j];
                     } else if (sg == 3) {
-                        zin[j] = y[j] + dt * (k2[j] - k1[j] / 3.f);
+                        zin[j] = cnf_stage_input(3, dt, y[j], k1[j], k2[j], k3[j]);
                         vb[j] = 3.f * dt * 0.125f * ybar[j] + dt * zb4[j];
                     } else {
-                        zin[j] = y[j] + dt * (k1[j] - k2[j] + k3[j]);
+                        zin[j] = cnf_stage_input(4, dt, y[j], k1[j], k2[j], k3[j]);
                         vb[j] = dt * 0.125f * ybar[j];
                     }
                 }
                 if (sg == 1) {
-                    t = t0;
+                    t = cnf_stage_time(1, S);
                     cl = dt * 0.125f;
                 } else if (sg == 2) {
-                    t = t0 + dt / 3.f;
+                    t = cnf_stage_time(2, S);
                     cl = 3.f * dt * 0.125f;
                 } else if (sg == 3) {
-                    t = t0 + 2.f * dt / 3.f;
+                    t = cnf_stage_time(3, S);
                     cl = 3.f * dt * 0.125f;
                 } else {
-                    t = t1;
+                    t = cnf_stage_time(4, S);
                     cl = dt * 0.125f;
                 }
                 float o[D], tr;
@@ -474,6 +460,10 @@ typedef void (*cnf_bwd_kernel_t)(CnfBwdArgs);
 // Defined once per hidden width, in nfx_cnf_bwd_h{1,2}.hip.
 template <int HT>
 cnf_bwd_kernel_t cnf_bwd_pick_ht(int d);
+template <>
+cnf_bwd_kernel_t cnf_bwd_pick_ht<1>(int d);
+template <>
+cnf_bwd_kernel_t cnf_bwd_pick_ht<2>(int d);
 
 template <int HT>
 cnf_bwd_kernel_t cnf_bwd_pick(int d) {

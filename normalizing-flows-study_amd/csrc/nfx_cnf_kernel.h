@@ -4,13 +4,13 @@
 #pragma once
 #include <math.h>
 
-#include "nfx_common.h"
+#include "nfx_tile_mlp.h"
 
 namespace nfx {
 
 // Packed weight image (floats), H = 32 HT, accumulator order = [tile][lane half][register]:
 //   w1  [HT][KS1][64]      A operand of layer 1 over k = 0..d ([z; t], t is input column d),
-//                          KS1 = (d + 2) / 2 k-steps, zero beyond k = d
+//                          KS1 = layer1_ksteps(d + 1) k-steps, zero beyond k = d
 //   b1  [HT][2][16]        layer-1 bias in accumulator order
 //   b2  [HT][2][16]
 //   w3  [d][HT][2][16]     W3[j, :] in accumulator order (VALU dots)
@@ -28,7 +28,7 @@ __host__ __device__ constexpr CnfLayout cnf_layout(int d, int HT) {
     CnfLayout L{};
     L.d = d;
     L.HT = HT;
-    L.KS1 = (d + 2) / 2;
+    L.KS1 = layer1_ksteps(d + 1);
     int o = 0;
     L.w1 = o; o += HT * L.KS1 * 64;
     L.b1 = o; o += HT * 32;
@@ -41,6 +41,61 @@ __host__ __device__ constexpr CnfLayout cnf_layout(int d, int HT) {
     return L;
 }
 
+// The discrete scheme (grid, step times, stage times and stage inputs), defined once: the forward
+// kernel runs it and the backward kernel (nfx_cnf_bwd_kernel.h) differentiates it, recomputing the
+// inputs of stages 2..4 with the same functions, so they round exactly as the forward's. The field
+// evaluation itself is written out in both kernels (DESIGN.md says why).
+struct CnfGrid {
+    int nsteps;         // grid points - 1; 0: equal times, the identity
+    float s0, s1, h;    // ascending grid s_k = k h + s0, last point s1
+    float sgn;          // t = sgn * s: -1 walks the grid downward (t_begin > t_end)
+};
+
+// The ascending grid of the fixed-step solver, in fp32 like the times tensor: n = ceil((s1 - s0)
+// / h + 1) points s_k = k h + s0 with the last one pinned to s1. A decreasing interval is the
+// negated-time problem (s = -t): the same grid walked downward with negative dt. False when the
+// grid has too many points.
+inline bool cnf_grid(float t_begin, float t_end, float step_size, CnfGrid& G) {
+    G.sgn = t_begin <= t_end ? 1.f : -1.f;
+    G.s0 = G.sgn * t_begin;
+    G.s1 = G.sgn * t_end;
+    G.h = step_size;
+    G.nsteps = 0;
+    if (t_begin != t_end) {
+        const float n = ceilf((G.s1 - G.s0) / step_size + 1.f);  // fp32 throughout, as the composite
+        if (!(n <= 16777216.f)) return false;
+        G.nsteps = (int)n - 1;
+    }
+    return true;
+}
+
+// Step k of the grid: from t0 to t1 = t0 + dt.
+struct CnfStep {
+    float t0, t1, dt;
+};
+__device__ __forceinline__ CnfStep cnf_step(const CnfGrid& G, int k) {
+#pragma clang fp contract(off)  // every mul/add rounds separately, as the torch composite's ops
+    const float sk = (float)k * G.h + G.s0;
+    const float sk1 = k + 1 == G.nsteps ? G.s1 : (float)(k + 1) * G.h + G.s0;
+    const float t0 = G.sgn * sk, t1 = G.sgn * sk1;
+    return {t0, t1, t1 - t0};
+}
+
+// Stage sg = 1..4 of the 3/8 rule, one coordinate: the stage input from the step's start y and the
+// earlier stage derivatives (k_i counts for i < sg only); and the stage time. The callers pass sg
+// as a constant inside their own branch on the stage.
+__device__ __forceinline__ float cnf_stage_input(int sg, float dt, float y, float k1, float k2, float k3) {
+#pragma clang fp contract(off)  // as cnf_step
+    if (sg == 1) return y;
+    if (sg == 2) return y + dt * k1 / 3.f;
+    if (sg == 3) return y + dt * (k2 - k1 / 3.f);
+    return y + dt * (k1 - k2 + k3);
+}
+__device__ __forceinline__ float cnf_stage_time(int sg, const CnfStep& S) {
+#pragma clang fp contract(off)  // as cnf_step
+    return sg == 1 ? S.t0 : sg == 2 ? S.t0 + S.dt / 3.f : sg == 3 ? S.t0 + 2.f * S.dt / 3.f : S.t1;
+}
+
 struct CnfArgs {
     const float* packed;
     const float* in;
@@ -48,29 +103,9 @@ struct CnfArgs {
     float* logdet;
     int64_t B, ntiles;
     int accumulate;
-    int nsteps;         // grid points - 1; 0: equal times, the identity
-    float s0, s1, h;    // ascending grid s_k = k h + s0, last point s1
-    float sgn;          // t = sgn * s: -1 walks the grid downward (t_begin > t_end)
+    CnfGrid g;
     float* traj;        // SAVE instantiations only: the trajectory the fused backward replays
 };
-
-// The ascending grid of the fixed-step solver, in fp32 like the times tensor: n = ceil((s1 - s0)
-// / h + 1) points s_k = k h + s0 with the last one pinned to s1. A decreasing interval is the
-// negated-time problem (s = -t): the same grid walked downward with negative dt. Fills sgn, s0,
-// s1, h, nsteps; false when the grid has too many points.
-inline bool cnf_grid(float t_begin, float t_end, float step_size, CnfArgs& A) {
-    A.sgn = t_begin <= t_end ? 1.f : -1.f;
-    A.s0 = A.sgn * t_begin;
-    A.s1 = A.sgn * t_end;
-    A.h = step_size;
-    A.nsteps = 0;
-    if (t_begin != t_end) {
-        const float n = ceilf((A.s1 - A.s0) / step_size + 1.f);  // fp32 throughout, as the composite
-        if (!(n <= 16777216.f)) return false;
-        A.nsteps = (int)n - 1;
-    }
-    return true;
-}
 
 // Trajectory of a SAVE launch (floats), nsteps = n >= 1: y_1 .. y_{n-1} step-major [n-1][B][d]
 // (the state at the start of steps 1 .. n-1; y_0 is the input), then the last step's result before
@@ -81,23 +116,16 @@ inline size_t cnf_traj_floats(int64_t B, int d, int nsteps) {
 
 constexpr int kCnfMaxD = 8;
 
-// Waves per SIMD the launch really reaches: two for H <= 64 (<= 256 registers; a handful of
-// outer-loop spills at H = 64, d >= 6), one for H = 128 (the register file to itself, no scratch).
-constexpr int cnf_waves_per_simd(int HT) { return HT <= 2 ? 2 : 1; }
-
+// (two waves per SIMD for H <= 64 means a handful of outer-loop spills at H = 64, d >= 6; H = 128
+// runs without scratch)
 template <int HT, int D, bool SAVE = false>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT)))) void cnf_kernel(CnfArgs A) {
+__attribute__((amdgpu_waves_per_eu(tile_waves_per_simd(HT), tile_waves_per_simd(HT)))) void cnf_kernel(CnfArgs A) {
     constexpr CnfLayout L = cnf_layout(D, HT);
-    constexpr int KS1 = L.KS1;
     constexpr bool W2REG = HT <= 2;
     constexpr int NLDS = W2REG ? L.w2 : L.total;
     extern __shared__ f32x4 lds4[];
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(A.packed);
-        for (int i = threadIdx.x; i < NLDS / 4; i += blockDim.x) lds4[i] = src[i];
-    }
-    __syncthreads();
+    stage_image(lds4, A.packed, NLDS / 4);
     const float* sm = reinterpret_cast<const float*>(lds4);
 
     const int lane = lane_id(), h = lane >> 5, col = lane & 31;
@@ -111,36 +139,24 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
 #pragma unroll
         for (int g = 0; g < HT * HT * 4; ++g) w2r[g] = wg[g * 64];
     }
-    const f32x4* w2s = reinterpret_cast<const f32x4*>(sm + L.w2) + lane;
-    const f32x4* c2s = reinterpret_cast<const f32x4*>(sm + L.c2) + lane;
 
-    // One evaluation of the field and its exact divergence for the wave's 32 samples. Both lane
-    // halves hold the same state (sample col); they own different hidden-unit rows of every
-    // accumulator tile and meet in halves_sum. The divergence sum_i W3[i, :] . (g2 * (W2 (g1 *
-    // W1[:, i]))) is summed over i inside the weights: it equals g2 . (C g1), ONE more H x H product
-    // beside layer 2 instead of d.
+    // One evaluation of the field and its exact divergence for the wave's 32 samples. The
+    // divergence sum_i W3[i, :] . (g2 * (W2 (g1 * W1[:, i]))) is summed over i inside the weights:
+    // it equals g2 . (C g1), ONE more H x H product beside layer 2 instead of d.
     auto field = [&](float t, const float (&z)[D], float (&v)[D], float& tr) {
-        const int oz = opaque_zero();  // no hoisting of the LDS operands out of the step loop
-        const float* s = sm + oz;
-        const f32x4* w2l = w2s + oz;
-        const f32x4* c2l = c2s + oz;
-        float xb[KS1];
+        const float* s = sm + opaque_zero();  // no hoisting of the LDS operands out of the step loop
+        const f32x4* w2l = reinterpret_cast<const f32x4*>(s + L.w2) + lane;
+        const f32x4* c2l = reinterpret_cast<const f32x4*>(s + L.c2) + lane;
+        float zt[D + 1];
 #pragma unroll
-        for (int ks = 0; ks < KS1; ++ks) {
-            const int k0 = 2 * ks, k1 = 2 * ks + 1;
-            const float a = k0 < D ? z[k0 < D ? k0 : 0] : (k0 == D ? t : 0.f);
-            const float b = k1 < D ? z[k1 < D ? k1 : 0] : (k1 == D ? t : 0.f);
-            xb[ks] = h ? b : a;
-        }
+        for (int j = 0; j < D; ++j) zt[j] = z[j];
+        zt[D] = t;
         f32x16 h1[HT];
+        layer1_preact<HT, D + 1>(s + L.w1, s + L.b1, lane, zt, h1);
 #pragma unroll
-        for (int ht = 0; ht < HT; ++ht) {
-            f32x16 a = load_bias16(s + L.b1 + ht * 32, h);
+        for (int ht = 0; ht < HT; ++ht)
 #pragma unroll
-            for (int ks = 0; ks < KS1; ++ks) a = mfma32(s[L.w1 + (ht * KS1 + ks) * 64 + lane], xb[ks], a);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) h1[ht][r] = tanhf(a[r]);
-        }
+            for (int r = 0; r < 16; ++r) h1[ht][r] = tanhf(h1[ht][r]);
         __builtin_amdgcn_sched_barrier(0);
         float pv[D];
 #pragma unroll
@@ -179,9 +195,7 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
 #pragma unroll
             for (int j = 0; j < D; ++j) {
                 __builtin_amdgcn_sched_barrier(0);
-                const f32x16 w3 = load_bias16(s + L.w3 + (j * HT + hto) * 32, h);
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pv[j] = fmaf(w3[r], a[r], pv[j]);
+                pv[j] = acc_dot16(s + L.w3 + (j * HT + hto) * 32, h, a, pv[j]);
                 asm volatile("" : "+v"(pv[j]));  // the dots of row j end before the next barrier
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -206,12 +220,10 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
         for (int j = 0; j < D; ++j) yc[j] = 0.f;
 
 #pragma unroll 1
-        for (int k = 0; k < A.nsteps; ++k) {
+        for (int k = 0; k < A.g.nsteps; ++k) {
 #pragma clang fp contract(off)  // every mul/add rounds separately, as the torch composite's ops
-            const float sk = (float)k * A.h + A.s0;
-            const float sk1 = k + 1 == A.nsteps ? A.s1 : (float)(k + 1) * A.h + A.s0;
-            const float t0 = A.sgn * sk, t1 = A.sgn * sk1;
-            const float dt = t1 - t0;
+            const CnfStep S = cnf_step(A.g, k);
+            const float dt = S.dt;
             if constexpr (SAVE) {
                 if (k > 0 && live && h == 0) {
                     float* tj = A.traj + ((int64_t)(k - 1) * A.B + srow) * D;
@@ -221,36 +233,36 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
             }
             float k1[D], k2[D], k3[D], zin[D];
             float l1 = 0.f, l2 = 0.f, l3 = 0.f;
-            float t = t0;
+            float t = cnf_stage_time(1, S);
 #pragma unroll
-            for (int j = 0; j < D; ++j) zin[j] = y[j];
+            for (int j = 0; j < D; ++j) zin[j] = cnf_stage_input(1, dt, y[j], 0.f, 0.f, 0.f);
 #pragma unroll 1
             for (int st = 0; st < 4; ++st) {
                 float v[D], tr;
                 field(t, zin, v, tr);
                 if (st == 0) {
-                    t = t0 + dt / 3.f;
+                    t = cnf_stage_time(2, S);
                     l1 = tr;
 #pragma unroll
                     for (int j = 0; j < D; ++j) {
                         k1[j] = v[j];
-                        zin[j] = y[j] + dt * k1[j] / 3.f;
+                        zin[j] = cnf_stage_input(2, dt, y[j], k1[j], 0.f, 0.f);
                     }
                 } else if (st == 1) {
-                    t = t0 + 2.f * dt / 3.f;
+                    t = cnf_stage_time(3, S);
                     l2 = tr;
 #pragma unroll
                     for (int j = 0; j < D; ++j) {
                         k2[j] = v[j];
-                        zin[j] = y[j] + dt * (k2[j] - k1[j] / 3.f);
+                        zin[j] = cnf_stage_input(3, dt, y[j], k1[j], k2[j], 0.f);
                     }
                 } else if (st == 2) {
-                    t = t1;
+                    t = cnf_stage_time(4, S);
                     l3 = tr;
 #pragma unroll
                     for (int j = 0; j < D; ++j) {
                         k3[j] = v[j];
-                        zin[j] = y[j] + dt * (k1[j] - k2[j] + k3[j]);
+                        zin[j] = cnf_stage_input(4, dt, y[j], k1[j], k2[j], k3[j]);
                     }
                 } else {
 #pragma unroll
@@ -269,17 +281,17 @@ __attribute__((amdgpu_waves_per_eu(cnf_waves_per_simd(HT), cnf_waves_per_simd(HT
         }
 
         if constexpr (SAVE) {
-            if (live && h == 0 && A.nsteps > 0) {
-                float* tj = A.traj + ((int64_t)(A.nsteps - 1) * A.B + srow) * D;
+            if (live && h == 0 && A.g.nsteps > 0) {
+                float* tj = A.traj + ((int64_t)(A.g.nsteps - 1) * A.B + srow) * D;
 #pragma unroll
                 for (int j = 0; j < D; ++j) tj[j] = y[j];
-                A.traj[(int64_t)A.nsteps * A.B * D + srow] = ld;
+                A.traj[(int64_t)A.g.nsteps * A.B * D + srow] = ld;
             }
         }
         if (live && h == 0) {
             float o[D];
             float lo = ld;
-            if (A.nsteps > 0) {  // the guards (equal times return the input untouched)
+            if (A.g.nsteps > 0) {  // the guards (equal times return the input untouched)
 #pragma unroll
                 for (int j = 0; j < D; ++j) o[j] = tclamp(nonfinite(y[j]) ? x0[j] : y[j], -10.f, 10.f);
                 lo = tclamp(nonfinite(ld) ? 0.f : ld, -10.f, 10.f);
@@ -299,6 +311,12 @@ typedef void (*cnf_kernel_t)(CnfArgs);
 // Defined once per hidden width, in nfx_cnf_h{1,2,4}.hip, as cnf_pick<HT>.
 template <int HT>
 cnf_kernel_t cnf_pick_ht(int d);
+template <>
+cnf_kernel_t cnf_pick_ht<1>(int d);
+template <>
+cnf_kernel_t cnf_pick_ht<2>(int d);
+template <>
+cnf_kernel_t cnf_pick_ht<4>(int d);
 
 // The compiled shapes, listed here only: d = 1..kCnfMaxD.
 template <int HT>
@@ -309,6 +327,10 @@ cnf_kernel_t cnf_pick(int d) {
 // The trajectory-saving instantiations (H <= 64), defined in nfx_cnf_bwd_h{1,2}.hip.
 template <int HT>
 cnf_kernel_t cnf_save_pick_ht(int d);
+template <>
+cnf_kernel_t cnf_save_pick_ht<1>(int d);
+template <>
+cnf_kernel_t cnf_save_pick_ht<2>(int d);
 template <int HT>
 cnf_kernel_t cnf_save_pick(int d) {
     return pick_range<1, kCnfMaxD>(d, [](auto D) -> cnf_kernel_t { return cnf_kernel<HT, D(), true>; });

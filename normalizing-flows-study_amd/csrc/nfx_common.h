@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/nfx.h"
 #include "nfx_pick.h"
 #include "nfx_tile.h"
@@ -218,6 +220,19 @@ int num_cus();
 int resident_grid(const void* kernel, int threads, size_t lds_bytes, int64_t work_groups);
 // Raise the dynamic-LDS limit of `kernel` when it needs more than 64 KiB.
 int prepare_lds(const void* kernel, size_t bytes);
+// Workgroup size of a tile-owner kernel (nfx_tile_mlp.h). Few tiles: one wave per workgroup, so
+// they spread over every CU; many: four waves share one staged weight image.
+int tile_owner_threads(int64_t ntiles);
+// prepare_lds, a resident_grid of at most work_groups, the launch of `kernel` with its one argument
+// struct *args, check_launch(name).
+int launch_resident(const void* kernel, void* args, int threads, size_t lds_bytes, int64_t work_groups,
+                    hipStream_t stream, const char* name);
+// The common I/O contract of the flow entries, reported as "<family>: ...": the direction value;
+// pointers that must not be null; that in and out are two buffers; check_io is the last two in turn.
+int check_direction(const char* family, int direction);
+int check_pointers(const char* family, std::initializer_list<const void*> required);
+int check_no_alias(const char* family, const void* in, const void* out);
+int check_io(const char* family, std::initializer_list<const void*> required, const void* in, const void* out);
 // out[i] = sum_w part[w * len + i] (float partials of nw workgroups, float64 result, fixed order).
 int train_sum_finish(const float* part, int nw, int len, double* out, hipStream_t s);
 // Reduce n float64 partials into sums[0] = total, sums[1] = (double)B (one 256-thread block).

@@ -4,10 +4,10 @@
 // leaky_relu(0.1) / exact gelu. ONE launch per call and direction.
 //
 // The reference's sampling direction is `dim` full conditioner calls from Python, about four ATen
-// launches per hidden layer each. Here a wave owns a tile of 32 samples from load to store, as in
-// the ResidualFlow kernel: hidden units on the accumulator rows of v_mfma_f32_32x32x2_f32, samples
-// on its columns, every layer's A fragments staged once per workgroup in LDS in the order that
-// makes a layer's accumulator tile the next layer's B operand. New here:
+// launches per hidden layer each. Here a wave owns a tile of 32 samples from load to store (the
+// shared core, nfx_tile_mlp.h): hidden units on the accumulator rows of v_mfma_f32_32x32x2_f32,
+// samples on its columns, every layer's A fragments staged once per workgroup in LDS in the order
+// that makes a layer's accumulator tile the next layer's B operand. New here:
 //   * the input is held like the first 8 registers of an accumulator tile (x_j in register creg(j)
 //     of lane half chalf(j)), so the d -> H layer is k-steps of an ordinary tile and needs no
 //     per-d instantiation; the H -> 2d layer is one more MFMA tile whose row j is mu_j and row
@@ -27,20 +27,8 @@
 
 namespace nfx {
 
-template <>
-naf_kernel_t naf_pick_ht<1>();
-template <>
-naf_kernel_t naf_pick_ht<2>();
-template <>
-naf_kernel_t naf_pick_ht<4>();
-
 static naf_kernel_t pick_naf(int HTM) {
-    switch (HTM) {
-        case 1: return naf_pick_ht<1>();
-        case 2: return naf_pick_ht<2>();
-        case 4: return naf_pick_ht<4>();
-        default: return nullptr;
-    }
+    return pick_of<1, 2, 4>(HTM, [](auto HT) -> naf_kernel_t { return naf_pick_ht<HT()>(); });
 }
 
 static const char* kNafFamily =
@@ -71,7 +59,7 @@ static bool naf_flags_ok(int nh, const int* widths, int flags) {
 static int naf_max_tiles(int nh, const int* widths) {
     int m = 1;
     for (int l = 0; l < nh; ++l) m = widths[l] > m ? widths[l] : m;
-    return naf_tiles(m);
+    return hidden_tiles(m);
 }
 
 struct NafPackArgs {
@@ -103,9 +91,9 @@ __global__ __launch_bounds__(kNafPackThreads) void naf_pack_kernel(NafPackArgs P
             const int cols = l == 0 ? d : P.lay.layer[l - 1].width;
             if (l == nh) {  // output layer: row j = mu_j, row 16 + j = alpha_j
                 if (o < L.v) {
-                    const ATileElem e = a_tile_elem(o - L.w);
-                    const int j = e.row & 15, k = 32 * e.tile + e.k;
-                    if (j < d && k < cols) v = naf_weight(R, (e.row >> 4) * d + j, k, cols);
+                    const RowCol e = a_image_elem(o - L.w, P.lay.layer[l - 1].nt);  // (one out tile)
+                    const int j = e.row & 15;
+                    if (j < d && e.col < cols) v = naf_weight(R, (e.row >> 4) * d + j, e.col, cols);
                 } else {
                     const int row = acc_vec_row(o - L.v), j = row & 15;
                     if (j < d) v = R.bias[(row >> 4) * d + j];
@@ -118,17 +106,16 @@ __global__ __launch_bounds__(kNafPackThreads) void naf_pack_kernel(NafPackArgs P
                     row = 32 * (t >> 9) + e.row;
                     k = e.k;
                 } else {
-                    const int ntin = P.lay.layer[l - 1].nt;
-                    const ATileElem e = a_tile_elem(o - L.w);
-                    row = 32 * (e.tile / ntin) + e.row;
-                    k = 32 * (e.tile % ntin) + e.k;
+                    const RowCol e = a_image_elem(o - L.w, P.lay.layer[l - 1].nt);
+                    row = e.row;
+                    k = e.col;
                 }
                 if (row < L.width && k < cols) v = naf_weight(R, row, k, cols);
             } else {  // bias, gamma, beta
-                const int t = o - L.v, which = t / (32 * L.nt), row = acc_vec_row(t % (32 * L.nt));
-                if (row < L.width) {
-                    if (which == 0) v = R.bias[row];
-                    else if (R.ln_weight) v = which == 1 ? R.ln_weight[row] : R.ln_bias[row];
+                const VecRow e = acc_rows_elem(o - L.v, L.nt);
+                if (e.row < L.width) {
+                    if (e.vec == 0) v = R.bias[e.row];
+                    else if (R.ln_weight) v = e.vec == 1 ? R.ln_weight[e.row] : R.ln_bias[e.row];
                 }
             }
         }
@@ -158,7 +145,7 @@ extern "C" int nfx_naf_pack(const NfxNafLayer* layers, int d, int n_hidden, cons
         return set_error(NFX_EINVAL, "naf_pack: bad shape d=%d n_hidden=%d", d, n_hidden);
     if (const char* why = naf_shape_problem(d, n_hidden, widths))
         return set_error(NFX_EUNSUPPORTED, "naf: d=%d n_hidden=%d %s (%s)", d, n_hidden, kNafFamily, why);
-    if (!layers || !packed) return set_error(NFX_EINVAL, "naf_pack: null pointer");
+    if (int rc = check_pointers("naf_pack", {layers, packed})) return rc;
     NafPackArgs P{};
     for (int l = 0; l <= n_hidden; ++l) {
         const NfxNafLayer& r = layers[l];
@@ -184,8 +171,7 @@ extern "C" int nfx_naf_flow(const float* packed, const float* in, float* out, fl
                             float clamp_log_scale, int direction, int accumulate, void* stream) {
     if (B < 0 || d <= 0 || n_hidden <= 0 || !widths)
         return set_error(NFX_EINVAL, "naf: bad shape B=%lld d=%d n_hidden=%d", (long long)B, d, n_hidden);
-    if (direction != NFX_FORWARD && direction != NFX_INVERSE)
-        return set_error(NFX_EINVAL, "naf: direction must be NFX_FORWARD or NFX_INVERSE");
+    if (int rc = check_direction("naf", direction)) return rc;
     if (const char* why = naf_shape_problem(d, n_hidden, widths))
         return set_error(NFX_EUNSUPPORTED, "naf: d=%d n_hidden=%d %s (%s)", d, n_hidden, kNafFamily, why);
     if (!naf_activation(activation))
@@ -196,8 +182,7 @@ extern "C" int nfx_naf_flow(const float* packed, const float* in, float* out, fl
     naf_kernel_t k = pick_naf(naf_max_tiles(n_hidden, widths));
     if (!k) return set_error(NFX_EUNSUPPORTED, "naf: no kernel for these widths");
     if (B == 0) return NFX_OK;
-    if (!packed || !in || !out || !log_det) return set_error(NFX_EINVAL, "naf: null pointer");
-    if (in == out) return set_error(NFX_EINVAL, "naf: in and out must not alias");
+    if (int rc = check_io("naf", {packed, in, out, log_det}, in, out)) return rc;
     const NafLayout lay = naf_layout(d, n_hidden, widths);
     NafArgs A{};
     A.packed = packed;
@@ -235,7 +220,6 @@ extern "C" int nfx_naf_flow(const float* packed, const float* in, float* out, fl
     const int64_t slots = (int64_t)num_cus() * per_cu;
     const int64_t want = (A.ntiles + slots - 1) / slots;
     A.tpw = want < 1 ? 1 : want > 4 ? 4 : (int)want;
-    const int grid = resident_grid((const void*)k, threads, lds, (A.ntiles + A.tpw - 1) / A.tpw);
-    k<<<grid, threads, lds, (hipStream_t)stream>>>(A);
-    return check_launch("naf_flow_kernel");
+    return launch_resident((const void*)k, &A, threads, lds, (A.ntiles + A.tpw - 1) / A.tpw, (hipStream_t)stream,
+                           "naf_flow_kernel");
 }

@@ -4,7 +4,7 @@
 #pragma once
 #include <math.h>
 
-#include "nfx_common.h"
+#include "nfx_tile_mlp.h"
 
 namespace nfx {
 
@@ -80,11 +80,6 @@ struct NafArgs {
     NafLayerDesc layer[kNafLayers];
 };
 
-// Padded hidden tiles of the widest layer: 1, 2 or 4 (a 96-wide layer runs the 4-tile kernel with
-// three tiles at work).
-constexpr int naf_tiles(int H) { return H <= 32 ? 1 : H <= 64 ? 2 : 4; }
-constexpr int naf_waves_per_simd(int HTM) { return HTM <= 2 ? 2 : 1; }
-
 // Input dimension on register r (< 8) of lane half h: 0..3 and 8..11 in the lower half, 4..7 and
 // 12..15 in the upper.
 __device__ __forceinline__ int naf_dim(int r, int h) { return crow(r, h); }
@@ -129,8 +124,8 @@ __device__ __forceinline__ float naf_sum_tiles(const float (&ts)[HTM]) {
 
 // LayerNorm over the true width (two passes: the mean, then the squared deviations of the true
 // rows only: a pad row's deviation is -mean, not 0) and the activation, for the tiles of one layer.
-// A sample is a column: its rows are this lane's registers over the tiles plus the other lane
-// half's, met in one halves_sum per pass.
+// A sample's rows are this lane's registers over the tiles plus the other lane half's, met in one
+// halves_sum per pass.
 template <int HTM>
 __device__ __forceinline__ void naf_norm_act(const float* s, const NafArgs& A, const NafLayerDesc& L, float eps,
                                              int lane, f32x16 (&t)[HTM]) {
@@ -258,22 +253,9 @@ __device__ __forceinline__ void naf_two_sum(float& s, float& c, float v) {
 
 template <int HTM>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(naf_waves_per_simd(HTM), naf_waves_per_simd(HTM)))) void naf_kernel(NafArgs A) {
+__attribute__((amdgpu_waves_per_eu(tile_waves_per_simd(HTM), tile_waves_per_simd(HTM)))) void naf_kernel(NafArgs A) {
     extern __shared__ f32x4 lds4[];
-    {
-        // the image, four 16-byte words in flight per thread
-        const f32x4* src = reinterpret_cast<const f32x4*>(A.packed);
-        int i = threadIdx.x;
-        for (; i + 768 < A.total4; i += 1024) {
-            const f32x4 a = src[i], b = src[i + 256], c = src[i + 512], e = src[i + 768];
-            lds4[i] = a;
-            lds4[i + 256] = b;
-            lds4[i + 512] = c;
-            lds4[i + 768] = e;
-        }
-        for (; i < A.total4; i += 256) lds4[i] = src[i];
-    }
-    __syncthreads();
+    stage_image(lds4, A.packed, A.total4);
     const float* sm = reinterpret_cast<const float*>(lds4);
 
     const int lane = lane_id(), h = lane >> 5, col = lane & 31;
@@ -346,5 +328,11 @@ typedef void (*naf_kernel_t)(NafArgs);
 // Defined once per padded width, in nfx_naf_h{1,2,4}.hip.
 template <int HTM>
 naf_kernel_t naf_pick_ht();
+template <>
+naf_kernel_t naf_pick_ht<1>();
+template <>
+naf_kernel_t naf_pick_ht<2>();
+template <>
+naf_kernel_t naf_pick_ht<4>();
 
 }  // namespace nfx

@@ -3,7 +3,7 @@
 //
 // The reference evaluates the inverse as a fixed-point loop of up to 100 MLP calls with a host sync
 // after each, and every log-det from a d x d Jacobian built by d autograd passes. Here a wave owns
-// a tile of 32 samples from load to store, exactly as in the ContinuousFlow kernel: the d -> H
+// a tile of 32 samples from load to store (the shared core, nfx_tile_mlp.h): the d -> H
 // layer is short v_mfma_f32_32x32x2_f32 k-steps, the H x H layer runs on A fragments read from LDS,
 // the H -> d layer is VALU dots across the two lane halves. New here:
 //   * the full Jacobian, one forward-mode tangent per input dimension,
@@ -22,20 +22,8 @@
 
 namespace nfx {
 
-template <>
-residual_kernel_t res_pick_ht<1>(int d);
-template <>
-residual_kernel_t res_pick_ht<2>(int d);
-template <>
-residual_kernel_t res_pick_ht<4>(int d);
-
 static residual_kernel_t pick_residual(int d, int HT) {
-    switch (HT) {
-        case 1: return res_pick_ht<1>(d);
-        case 2: return res_pick_ht<2>(d);
-        case 4: return res_pick_ht<4>(d);
-        default: return nullptr;
-    }
+    return pick_of<1, 2, 4>(HT, [&](auto HT_) -> residual_kernel_t { return res_pick_ht<HT_()>(d); });
 }
 
 static bool res_family(int d, int H) { return d >= 1 && d <= kResMaxD && H >= 1 && H <= kResMaxH; }
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(kResPackThreads) void residual_pack_kernel(ResPackA
     float sc[3];
     for (int l = 0; l < 3; ++l) sc[l] = res_spectral_scale(P.layer[l], tv, tu);
     const int d = P.d, H = P.H;
-    const int HT = res_tiles(H);
+    const int HT = hidden_tiles(H);
     const ResLayout L = res_layout(d, HT);
     const float *w1 = P.layer[0].w, *w2 = P.layer[1].w, *w3 = P.layer[2].w;
     for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < L.total; o += gridDim.x * blockDim.x) {
@@ -109,18 +97,17 @@ __global__ __launch_bounds__(kResPackThreads) void residual_pack_kernel(ResPackA
             const int row = acc_vec_row(o - (second ? L.b2 : L.b1));
             if (row < H) v = second ? P.layer[1].b[row] : P.layer[0].b[row];
         } else if (o < L.w3) {  // w1c: column i of W1
-            const int t = o - L.w1c, i = t / (32 * HT), row = acc_vec_row(t % (32 * HT));
-            if (row < H) v = w1[row * d + i] * sc[0];
+            const VecRow e = acc_rows_elem(o - L.w1c, HT);
+            if (e.row < H) v = w1[e.row * d + e.vec] * sc[0];
         } else if (o < L.b3) {  // w3: row j of W3
-            const int t = o - L.w3, j = t / (32 * HT), row = acc_vec_row(t % (32 * HT));
-            if (row < H) v = w3[j * H + row] * sc[2];
+            const VecRow e = acc_rows_elem(o - L.w3, HT);
+            if (e.row < H) v = w3[e.vec * H + e.row] * sc[2];
         } else if (o < L.w2) {  // b3
             const int j = o - L.b3;
             if (j < d) v = P.layer[2].b[j];
         } else {  // w2: A operand over (out row k, hidden input j)
-            const ATileElem e = a_tile_elem(o - L.w2);
-            const int k = 32 * (e.tile / HT) + e.row, j = 32 * (e.tile % HT) + e.k;
-            if (k < H && j < H) v = w2[k * H + j] * sc[1];
+            const RowCol e = a_image_elem(o - L.w2, HT);
+            if (e.row < H && e.col < H) v = w2[e.row * H + e.col] * sc[1];
         }
         P.packed[o] = v;
     }
@@ -132,7 +119,7 @@ using namespace nfx;
 
 extern "C" size_t nfx_residual_packed_floats(int d, int H) {
     if (!res_family(d, H)) return 0;
-    return (size_t)res_layout(d, res_tiles(H)).total;
+    return (size_t)res_layout(d, hidden_tiles(H)).total;
 }
 
 extern "C" int nfx_residual_supported(int64_t B, int d, int H, int activation) {
@@ -146,8 +133,7 @@ extern "C" int nfx_residual_pack(const float* w1, const float* b1, const float* 
     if (d <= 0 || H <= 0) return set_error(NFX_EINVAL, "residual_pack: bad shape d=%d H=%d", d, H);
     if (!res_family(d, H))
         return set_error(NFX_EUNSUPPORTED, "residual: d=%d H=%d outside the compiled family (d<=8, H<=128)", d, H);
-    if (!w1 || !b1 || !u1 || !v1 || !w2 || !b2 || !u2 || !v2 || !w3 || !b3 || !u3 || !v3 || !packed)
-        return set_error(NFX_EINVAL, "residual_pack: null pointer");
+    if (int rc = check_pointers("residual_pack", {w1, b1, u1, v1, w2, b2, u2, v2, w3, b3, u3, v3, packed})) return rc;
     ResPackArgs P{};
     P.layer[0] = ResLayerRaw{w1, b1, u1, v1, c1, H, d};
     P.layer[1] = ResLayerRaw{w2, b2, u2, v2, c2, H, H};
@@ -166,8 +152,7 @@ extern "C" int nfx_residual_flow(const float* packed, const float* in, float* ou
                                  int accumulate, void* stream) {
     if (B < 0 || d <= 0 || H <= 0)
         return set_error(NFX_EINVAL, "residual: bad shape B=%lld d=%d H=%d", (long long)B, d, H);
-    if (direction != NFX_FORWARD && direction != NFX_INVERSE)
-        return set_error(NFX_EINVAL, "residual: direction must be NFX_FORWARD or NFX_INVERSE");
+    if (int rc = check_direction("residual", direction)) return rc;
     if (neumann_terms < 0 || max_iter < 0)
         return set_error(NFX_EINVAL, "residual: neumann_terms=%d and max_iter=%d must not be negative", neumann_terms,
                          max_iter);
@@ -175,12 +160,11 @@ extern "C" int nfx_residual_flow(const float* packed, const float* in, float* ou
         return set_error(NFX_EUNSUPPORTED, "residual: d=%d H=%d outside the compiled family (d<=8, H<=128)", d, H);
     if (!res_activation(activation))
         return set_error(NFX_EUNSUPPORTED, "residual: activation=%d is not one of NFX_RESIDUAL_*", activation);
-    const int HT = res_tiles(H);
+    const int HT = hidden_tiles(H);
     residual_kernel_t k = pick_residual(d, HT);
     if (!k) return set_error(NFX_EUNSUPPORTED, "residual: no kernel for d=%d H=%d", d, H);
     if (B == 0) return NFX_OK;
-    if (!packed || !in || !out || !log_det) return set_error(NFX_EINVAL, "residual: null pointer");
-    if (in == out) return set_error(NFX_EINVAL, "residual: in and out must not alias");
+    if (int rc = check_io("residual", {packed, in, out, log_det}, in, out)) return rc;
     ResArgs A{};
     A.packed = packed;
     A.in = in;
@@ -195,13 +179,7 @@ extern "C" int nfx_residual_flow(const float* packed, const float* in, float* ou
     A.max_iter = max_iter;
     A.tol = tol;
     const size_t lds = (size_t)res_layout(d, HT).total * sizeof(float);
-    // Few tiles: one wave per workgroup, so they spread over every CU; many: four waves share one
-    // staged weight image.
-    const int threads = A.ntiles >= (int64_t)8 * num_cus() ? 256 : 64;
-    const int nw = threads / 64;
-    int rc = prepare_lds((const void*)k, lds);
-    if (rc) return rc;
-    const int grid = resident_grid((const void*)k, threads, lds, (A.ntiles + nw - 1) / nw);
-    k<<<grid, threads, lds, (hipStream_t)stream>>>(A);
-    return check_launch("residual_flow_kernel");
+    const int threads = tile_owner_threads(A.ntiles), nw = threads / 64;
+    return launch_resident((const void*)k, &A, threads, lds, (A.ntiles + nw - 1) / nw, (hipStream_t)stream,
+                           "residual_flow_kernel");
 }

@@ -3,13 +3,13 @@
 #pragma once
 #include <math.h>
 
-#include "nfx_common.h"
+#include "nfx_tile_mlp.h"
 
 namespace nfx {
 
 // Packed weight image (floats), hidden width padded to HP = 32 HT (padding rows and columns are 0;
 // every activation maps 0 to 0, so the padding never reaches a result). All of it is staged in LDS.
-//   w1  [HT][KS1][64]      A operand of layer 1 over k = 0..d-1, KS1 = (d + 1) / 2 k-steps
+//   w1  [HT][KS1][64]      A operand of layer 1 over k = 0..d-1, KS1 = layer1_ksteps(d) k-steps
 //   b1  [HT][2][16]        layer-1 bias in accumulator order
 //   b2  [HT][2][16]
 //   w1c [d][HT][2][16]     column i of W1 in accumulator order: the seed of tangent i
@@ -25,7 +25,7 @@ __host__ __device__ constexpr ResLayout res_layout(int d, int HT) {
     ResLayout L{};
     L.d = d;
     L.HT = HT;
-    L.KS1 = (d + 1) / 2;
+    L.KS1 = layer1_ksteps(d);
     int o = 0;
     L.w1 = o; o += HT * L.KS1 * 64;
     L.b1 = o; o += HT * 32;
@@ -54,12 +54,6 @@ struct ResArgs {
 
 constexpr int kResMaxD = 8;
 constexpr int kResMaxH = 128;
-
-// Padded hidden tiles of a hidden width: 32 -> 1, 64 -> 2, up to 128 -> 4 (96 runs the HT = 4 kernels).
-constexpr int res_tiles(int H) { return H <= 32 ? 1 : H <= 64 ? 2 : 4; }
-
-// Waves per SIMD, as the ContinuousFlow kernels: two up to 64 hidden units, one at 128.
-constexpr int res_waves_per_simd(int HT) { return HT <= 2 ? 2 : 1; }
 
 // Tangent chains evaluated beside one value chain (the accumulator tiles of a pass are 1 + this).
 constexpr int res_tangent_group(int HT, int D) {
@@ -118,19 +112,20 @@ __device__ __forceinline__ f32x16 res_dact16(int act, const f32x16& o) {
 // One evaluation of the MLP for the wave's 32 samples: out = W3 h2 + b3 and, beside the value
 // chain, NT tangent chains for the input dimensions I0 .. I0 + NT - 1,
 //   Jc[t][j] = d out_j / d z_(I0 + t) = W3[j, :] . (g2 * (W2 (g1 * W1[:, I0 + t]))).
-// Both lane halves hold the same sample (column lane & 31); they own different hidden-unit rows of
-// every accumulator tile and meet in halves_sum. A layer-2 A fragment is read from LDS once and
-// feeds the value chain and every tangent chain of the pass.
+// A layer-2 A fragment is read from LDS once and feeds the value chain and every tangent chain of
+// the pass.
 template <int HT, int D, int NT, int I0>
 __device__ __forceinline__ void res_eval(const float* sm, int act, int lane, const float (&z)[D], float (&out)[D],
                                          float (&Jc)[NT > 0 ? NT : 1][D]) {
     constexpr ResLayout L = res_layout(D, HT);
-    constexpr int KS1 = L.KS1;
     const int h = lane >> 5;
     const int oz = opaque_zero();  // no hoisting of the LDS operands out of the caller's loops
     const float* s = sm + oz;
     const f32x4* w2l = reinterpret_cast<const f32x4*>(s + L.w2) + lane;
 
+    // Layer 1 is layer1_preact's code written out: calling it here moved the register allocation of
+    // residual_kernel<4, 6> and <4, 8> to 32 and 28 more scratch bytes per lane.
+    constexpr int KS1 = L.KS1;
     float xb[KS1];
 #pragma unroll
     for (int ks = 0; ks < KS1; ++ks) {
@@ -191,17 +186,14 @@ __device__ __forceinline__ void res_eval(const float* sm, int act, int lane, con
                 for (int r = 0; r < 16; ++r) c[t][r] *= g2[r];
         }
         // (the barriers keep the compiler from issuing every LDS operand of the evaluation ahead
-        // of its use, as in the ContinuousFlow kernel)
+        // of its use)
 #pragma unroll
         for (int j = 0; j < D; ++j) {
             __builtin_amdgcn_sched_barrier(0);
             const f32x16 w3 = load_bias16(s + L.w3 + (j * HT + hto) * 32, h);
+            pv[j] = acc_dot16(w3, a, pv[j]);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) pv[j] = fmaf(w3[r], a[r], pv[j]);
-#pragma unroll
-            for (int t = 0; t < NT; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pj[t][j] = fmaf(w3[r], c[t][r], pj[t][j]);
+            for (int t = 0; t < NT; ++t) pj[t][j] = acc_dot16(w3, c[t], pj[t][j]);
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -267,15 +259,11 @@ __device__ __forceinline__ float res_neumann(const float (&J)[D][D], int nterms)
 
 template <int HT, int D>
 __global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(res_waves_per_simd(HT), res_waves_per_simd(HT)))) void residual_kernel(ResArgs A) {
+__attribute__((amdgpu_waves_per_eu(tile_waves_per_simd(HT), tile_waves_per_simd(HT)))) void residual_kernel(ResArgs A) {
     constexpr ResLayout L = res_layout(D, HT);
     constexpr int TG = res_tangent_group(HT, D);
     extern __shared__ f32x4 lds4[];
-    {
-        const f32x4* src = reinterpret_cast<const f32x4*>(A.packed);
-        for (int i = threadIdx.x; i < L.total / 4; i += blockDim.x) lds4[i] = src[i];
-    }
-    __syncthreads();
+    stage_image(lds4, A.packed, L.total / 4);
     const float* sm = reinterpret_cast<const float*>(lds4);
 
     const int lane = lane_id(), h = lane >> 5, col = lane & 31;
@@ -338,6 +326,12 @@ typedef void (*residual_kernel_t)(ResArgs);
 // Defined once per padded width, in nfx_residual_h{1,2,4}.hip, as res_pick<HT>.
 template <int HT>
 residual_kernel_t res_pick_ht(int d);
+template <>
+residual_kernel_t res_pick_ht<1>(int d);
+template <>
+residual_kernel_t res_pick_ht<2>(int d);
+template <>
+residual_kernel_t res_pick_ht<4>(int d);
 
 // The compiled shapes, listed here only: d = 1..kResMaxD.
 template <int HT>

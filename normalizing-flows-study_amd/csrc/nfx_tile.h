@@ -46,6 +46,11 @@ __host__ __device__ constexpr ATileElem a_tile_elem(int t) {
 // f32x4 index, in units of the 64 lanes, of quad rq of a tile.
 __host__ __device__ constexpr int a_tile(int ot, int kt, int NK) { return ot * NK + kt; }
 __host__ __device__ constexpr int a_quad(int tile, int rq) { return tile * 4 + rq; }
+// Decode of a whole [ot][kt] image with NK k tiles: (out row, contraction column) of float offset t.
+__host__ __device__ constexpr RowCol a_image_elem(int t, int NK) {
+    const ATileElem e = a_tile_elem(t);
+    return {32 * (e.tile / NK) + e.row, 32 * (e.tile % NK) + e.k};
+}
 
 // Layer-1 A operand [ht][ks][64] with KS1 k-steps: offset t holds W1[row][col], col = 2 ks + (l >> 5).
 __host__ __device__ constexpr RowCol a1_elem(int t, int KS1) {
@@ -56,6 +61,14 @@ __host__ __device__ constexpr RowCol a1_elem(int t, int KS1) {
 // Per-row vectors (biases, W3 rows for VALU dots) in accumulator order [tile][lane half][16]:
 // the row that offset t holds.
 __host__ __device__ constexpr int acc_vec_row(int t) { return 32 * (t >> 5) + crow(t & 15, (t >> 4) & 1); }
+// A run [n][HT][2][16] of such vectors, each over HT tiles (the rows of W3, the columns of W1,
+// bias / gamma / beta): the vector that offset t lies in, and the row it holds.
+struct VecRow {
+    int vec, row;
+};
+__host__ __device__ constexpr VecRow acc_rows_elem(int t, int HT) {
+    return {t / (32 * HT), acc_vec_row(t % (32 * HT))};
+}
 
 // ---- accumulator tiles dumped to memory, 1,024 values per tile ----
 // [r][64] (register-major, lane-contiguous stores): the element at offset t, and the offset of
@@ -95,6 +108,29 @@ constexpr bool a_tile_encode_inverts() {
     }
     return true;
 }
+// a 2 x 3 image: the float a kernel reads as element rr of quad rq of tile (ot, kt) in lane l is the
+// one the pack decoded, and the decode stays inside the image
+constexpr bool a_image_encode_inverts() {
+    constexpr int NO = 2, NK = 3;
+    for (int t = 0; t < NO * NK * 1024; ++t) {
+        const RowCol e = a_image_elem(t, NK);
+        if (e.row < 0 || e.row >= 32 * NO || e.col < 0 || e.col >= 32 * NK) return false;
+        const int k = e.col & 31, r = creg(k), lane = (e.row & 31) + 32 * chalf(k);
+        if ((a_quad(a_tile(e.row >> 5, e.col >> 5, NK), r >> 2) * 64 + lane) * 4 + (r & 3) != t) return false;
+    }
+    return true;
+}
+// three vectors over two tiles: load_bias16 of tile ht of vector n, lane half h, register r reads
+// offset (n HT + ht) 32 + 16 h + r
+constexpr bool acc_rows_encode_inverts() {
+    constexpr int N = 3, HT = 2;
+    for (int t = 0; t < N * HT * 32; ++t) {
+        const VecRow e = acc_rows_elem(t, HT);
+        if (e.vec < 0 || e.vec >= N || e.row < 0 || e.row >= 32 * HT) return false;
+        if ((e.vec * HT + (e.row >> 5)) * 32 + 16 * chalf(e.row & 31) + creg(e.row & 31) != t) return false;
+    }
+    return true;
+}
 constexpr bool dumps_round_trip() {
     bool seen[32 * 32] = {};
     for (int t = 0; t < 1024; ++t) {
@@ -108,6 +144,8 @@ constexpr bool dumps_round_trip() {
 static_assert(crow_round_trips(), "creg/chalf invert crow for all 32 rows");
 static_assert(a_tile_visits_all(), "A-operand decode is a bijection onto the tile");
 static_assert(a_tile_encode_inverts(), "A-operand encode inverts the decode");
+static_assert(a_image_encode_inverts(), "[ot][kt] image decode inverts the kernels' a_tile/a_quad index");
+static_assert(acc_rows_encode_inverts(), "accumulator-order vector runs decode to the offset load_bias16 reads");
 static_assert(dumps_round_trip(), "accumulator dump orders are bijections");
 static_assert(acc_vec_row(32 + 16 + 5) == 32 + crow(5, 1), "accumulator-order vector");
 }  // namespace tile_check
