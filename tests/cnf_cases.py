@@ -48,12 +48,13 @@ B_MAX = 4099
 
 
 @functools.lru_cache(maxsize=None)
-def parity_case(d, H, direction):
-    """(flow, x [B_MAX, d], (y32, ld32), (y64, ld64)): the shared-weights flow, its inputs, and
+def parity_case(d, H, direction, B_max=B_MAX):
+    """(flow, x [B_max, d], (y32, ld32), (y64, ld64)): the shared-weights flow, its inputs, and
     the fp32 and float64 CPU composites in `direction`. Rows are independent, so a test at a
-    smaller batch slices these; computed once per session and never modified."""
+    smaller batch slices these; computed once per session and never modified.
+    (test_gpu_tile_instantiations.py draws 33 rows per case: `B_max=33`.)"""
     flow = make_flow(d, H)
-    x = make_inputs(B_MAX, d, seed=3 + (direction > 0))
+    x = make_inputs(B_max, d, seed=3 + (direction > 0))
     c32 = composite(flow, x, direction)
     c64 = composite(as_double(flow), x.double(), direction)
     return flow, x, c32, c64

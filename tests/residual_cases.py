@@ -70,13 +70,13 @@ B_MAX = 4099
 
 
 @functools.lru_cache(maxsize=None)
-def parity_case(d, H, act, lipschitz, direction):
-    """(flow, x [B_MAX, d], (y32, ld32), (y64, ld64)): the shared-weights flow, its inputs, and the
+def parity_case(d, H, act, lipschitz, direction, B_max=B_MAX):
+    """(flow, x [B_max, d], (y32, ld32), (y64, ld64)): the shared-weights flow, its inputs, and the
     fp32 and float64 CPU composites in `direction`. Rows are independent (the composite's stopping
     rule is per sample), so a test at a smaller batch slices these; computed once per session and
-    never modified."""
+    never modified. (test_gpu_tile_instantiations.py draws 33 rows per case: `B_max=33`.)"""
     flow = make_flow(d, H, act, lipschitz)
-    x = make_inputs(B_MAX, d, seed=3 + (direction > 0))
+    x = make_inputs(B_max, d, seed=3 + (direction > 0))
     c32 = composite(flow, x, direction)
     c64 = composite(as_double(flow), x.double(), direction)
     return flow, x, c32, c64

@@ -19,7 +19,9 @@ import functools
 import pytest
 import torch
 
+import naf_cases
 import nfs_amd
+import residual_cases
 from nfs_amd import _lib
 from nfs_amd.flows import arqs as _aq
 from nfs_amd.flows import autoregressive as _ar
@@ -86,6 +88,14 @@ def _extra_model(kind):
     if kind == "made_d12_h256":
         return _perturb(N([nfs_amd.MaskedAutoregressiveFlow(12, 256), nfs_amd.InverseAutoregressiveFlow(12, 256)]),
                         0.02, 33), 12
+    # the two tile-owner families whose outputs and packed images come from torch.empty too; their
+    # own redraws (residual_cases, naf_cases) put the spectral normalisation and the clamps to work
+    if kind == "residual_d2_h64":
+        return N([residual_cases.make_flow(2, 64, "tanh", 1.8)]), 2
+    if kind == "residual_d5_h40":  # a kernel with scratch and a ragged tangent group
+        return N([residual_cases.make_flow(5, 40, "elu", 0.9)]), 5
+    if kind == "naf_d4_h64":
+        return N([naf_cases.make_flow(4, (64, 64), "gelu")]), 4
     raise ValueError(kind)
 
 
@@ -204,7 +214,7 @@ def _grad_op(kind, B, dev, train=False, sampling=False, setup=None):
 
 
 # ---- eval ---------------------------------------------------------------------------------------
-EVAL_KINDS = KINDS + ["cnf_d2_h64", "cnf_d5_h32", "spline_d2"]
+EVAL_KINDS = KINDS + ["cnf_d2_h64", "cnf_d5_h32", "spline_d2", "residual_d2_h64", "residual_d5_h40", "naf_d4_h64"]
 
 
 @pytest.mark.parametrize("kind", EVAL_KINDS)

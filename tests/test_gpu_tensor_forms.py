@@ -8,8 +8,9 @@ model per family runs every direction and the gradient pass with plain tensors (
 allocator-aligned) and with the same values held in another form: column-major, row-strided, a
 column slice of a wider tensor, a contiguous view that starts one float into a larger buffer;
 upstream gradients with stride 0, transposed, or one float into a buffer; parameters whose storage
-is transposed, masks and BatchNorm buffers one float into a buffer. Results must be bit-identical
-to the plain run, and the odd tensor's address must never reach the library (a copy was made).
+is transposed, masks, BatchNorm buffers and spectral-norm vectors one float into a buffer. Results
+must be bit-identical to the plain run, and the odd tensor's address must never reach the library
+(a copy was made).
 
 The entry points that promise to take a 4-byte-aligned base themselves (nfx_linear_*: the scalar
 -load GEMM variants and the scalar column-sum kernel; nfx_flowbn_*: the scalar body) are called
@@ -47,7 +48,13 @@ FAMILIES = {
     "arqs": ("arqs_d4_k5", False, False),
     "cnf": ("cnf_d2_h64", False, False),
     "flowbn": ("realnvp_bn_between", True, False),
+    "residual": ("residual_d5_h40", False, False),
+    "naf": ("naf_d4_h64", False, False),
 }
+# The residual flow and the NAF have no backward kernel: their gradients recompute through the torch
+# composite (STATS["torch"] == 1), which `_grad` refuses, so they run the eval tests only.
+EVAL_ONLY_FAMILIES = ["residual", "naf"]
+GRAD_FAMILIES = [f for f in FAMILIES if f not in EVAL_ONLY_FAMILIES]
 EVAL_FAMILIES = [f for f in FAMILIES if f != "affine_fused_train"]
 
 
@@ -92,10 +99,11 @@ def weights_transposed(m):
 
 
 def buffers_off4(m):
-    """Every mask and every BatchNorm running statistic one float into a larger buffer."""
+    """Every mask, every BatchNorm running statistic and every spectral-norm vector one float into a
+    larger buffer."""
     n = 0
     for mod in m.modules():
-        for name in ("mask", "running_mean", "running_var"):
+        for name in ("mask", "running_mean", "running_var", "u", "v"):
             b = mod._buffers.get(name)
             if b is not None:
                 mod._buffers[name] = off4(b)
@@ -213,7 +221,7 @@ def test_eval_x_form(cuda_device, seen, family, form, B):
 
 
 @pytest.mark.parametrize("form", list(X_FORMS))
-@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("family", GRAD_FAMILIES)
 @pytest.mark.parametrize("B", BATCHES)
 def test_gradient_x_form(cuda_device, seen, family, form, B):
     m, d = _model(family, cuda_device, True)
@@ -238,7 +246,7 @@ G_FORMS = {"stride0": (_stride0, True), "non_contiguous": (_transposed, False), 
 
 
 @pytest.mark.parametrize("form", list(G_FORMS))
-@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("family", GRAD_FAMILIES)
 @pytest.mark.parametrize("B", BATCHES)
 def test_gradient_cotangent_form(cuda_device, seen, family, form, B):
     fn, const = G_FORMS[form]
@@ -251,20 +259,32 @@ def test_gradient_cotangent_form(cuda_device, seen, family, form, B):
 
 
 # ---- parameters and buffers in another form -----------------------------------------------------
+def _parameter_form_eval(family, form, B, dev):
+    m, d = _model(family, dev, False)
+    PARAM_FORMS[form](m)
+    got = _eval(m, _inputs(B, d, dev))
+    _assert_same(got, _plain_eval(family, B, dev), (family, form, "eval"))
+
+
 # (the CNF has neither a mask nor a BatchNorm: nothing for buffers_off4 to move)
-@pytest.mark.parametrize("family,form", [(fam, form) for fam in FAMILIES for form in PARAM_FORMS
+@pytest.mark.parametrize("family,form", [(fam, form) for fam in GRAD_FAMILIES for form in PARAM_FORMS
                                          if (fam, form) != ("cnf", "buffers_off4")])
 @pytest.mark.parametrize("B", BATCHES)
 def test_parameter_form(cuda_device, family, form, B):
     if family != "affine_fused_train":
-        m, d = _model(family, cuda_device, False)
-        PARAM_FORMS[form](m)
-        got = _eval(m, _inputs(B, d, cuda_device))
-        _assert_same(got, _plain_eval(family, B, cuda_device), (family, form, "eval"))
+        _parameter_form_eval(family, form, B, cuda_device)
     m, d = _model(family, cuda_device, True)
     PARAM_FORMS[form](m)
     got = _grad(family, m, _inputs(B, d, cuda_device, 1.2), _cotangents(B, d, cuda_device, False))
     _assert_same(got, _plain_grad(family, B, False, cuda_device), (family, form, "gradients"))
+
+
+@pytest.mark.parametrize("form", list(PARAM_FORMS))
+@pytest.mark.parametrize("family", EVAL_ONLY_FAMILIES)
+@pytest.mark.parametrize("B", BATCHES)
+def test_parameter_form_eval_only(cuda_device, family, form, B):
+    """The eval half of test_parameter_form for the families without a backward kernel."""
+    _parameter_form_eval(family, form, B, cuda_device)
 
 
 def test_dense_copies_only_what_it_must(cuda_device):
