@@ -804,6 +804,46 @@ int nfx_naf_flow(const float* packed, const float* in, float* out, float* log_de
                  const int* widths, int activation, int flags, float clamp_alpha, float clamp_log_scale,
                  int direction, int accumulate, void* stream);
 
+/* Backward of NFX_INVERSE (the density direction, the one an NLL step uses): the gradients autograd
+ * gives for the composite, of <gz, out> + <gld, log_det>, with respect to the input and every
+ * parameter. The conditioner is recomputed from x inside the kernel, so the forward saves nothing.
+ * Kernel family: 1 <= d <= 16, 1 <= n_hidden <= 4, every width in 1..64 (all four activations,
+ * LayerNorm on or off, residual blocks), and an LDS need (the backward image and four 32 x 33
+ * transposition tiles) within 160 KiB: every such shape fits, [64, 64, 64, 64] at d = 16 included.
+ * nfx_naf_backward_supported is the host-only check; the size functions return 0 outside the family.
+ *   nfx_naf_pack_backward             the forward image, then every layer's transposed A operand:
+ *                                     nfx_naf_backward_packed_floats floats. Arguments as nfx_naf_pack.
+ *   nfx_naf_backward_slots            waves that write a partial sum for batch B (capped; a wave per
+ *   nfx_naf_backward_block_threads    32-row tile below the cap), and the workgroup size (64 or 256).
+ *   nfx_naf_backward_workspace_floats the slots, the float64 totals, the waves' kept activations. Any
+ *                                     content on entry; 16-byte aligned.
+ *   nfx_naf_backward                  layers[0 .. n_hidden] as packed (the masks are applied to the
+ *                                     weight gradients: mask o dW); grads[0 .. n_hidden] the outputs in
+ *                                     nn.Linear / nn.LayerNorm layout, a NULL member is not written.
+ *                                     gx [B, d] must not alias x or gz. Three launches (naf_bwd_kernel,
+ *                                     naf_bwd_reduce_kernel, naf_bwd_finish_kernel), no float atomics:
+ *                                     the same inputs give the same bits. A row with a non-finite input
+ *                                     element or conditioner output adds nothing to any parameter
+ *                                     gradient and gets gx = 0. B == 0 is a no-op.
+ * ------------------------------------------------------------------------------------- */
+typedef struct NfxNafLayerGrad {
+    float* weight;    /* [out, in] */
+    float* bias;      /* [out] */
+    float* ln_weight; /* [out], or NULL */
+    float* ln_bias;   /* [out], or NULL */
+} NfxNafLayerGrad;
+int nfx_naf_backward_supported(int64_t B, int d, int n_hidden, const int* widths, int activation, int flags);
+size_t nfx_naf_backward_packed_floats(int d, int n_hidden, const int* widths);
+int nfx_naf_pack_backward(const NfxNafLayer* layers, int d, int n_hidden, const int* widths, float* packed,
+                          void* stream);
+size_t nfx_naf_backward_slots(int64_t B, int d, int n_hidden, const int* widths);
+size_t nfx_naf_backward_block_threads(int64_t B, int d, int n_hidden, const int* widths);
+size_t nfx_naf_backward_workspace_floats(int64_t B, int d, int n_hidden, const int* widths);
+int nfx_naf_backward(const float* packed, const NfxNafLayer* layers, const float* x, const float* gz,
+                     const float* gld, float* gx, const NfxNafLayerGrad* grads, float* workspace, int64_t B, int d,
+                     int n_hidden, const int* widths, int activation, int flags, float clamp_alpha,
+                     float clamp_log_scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,23 +45,6 @@ static const char* naf_shape_problem(int d, int nh, const int* widths) {
     return nullptr;
 }
 
-static bool naf_activation(int a) { return a >= NFX_NAF_RELU && a <= NFX_NAF_GELU; }
-
-// A residual flag needs a layer above the first whose width equals the one below it.
-static bool naf_flags_ok(int nh, const int* widths, int flags) {
-    if (flags & ~(NFX_NAF_LAYER_NORM | ((2 << kNafMaxHidden) - 2))) return false;
-    for (int l = 0; l < kNafMaxHidden; ++l)
-        if (flags & NFX_NAF_RESIDUAL(l))
-            if (l < 1 || l >= nh || widths[l] != widths[l - 1]) return false;
-    return true;
-}
-
-static int naf_max_tiles(int nh, const int* widths) {
-    int m = 1;
-    for (int l = 0; l < nh; ++l) m = widths[l] > m ? widths[l] : m;
-    return hidden_tiles(m);
-}
-
 struct NafPackArgs {
     NfxNafLayer raw[kNafLayers];
     NafLayout lay;

@@ -84,6 +84,16 @@ class NfxNafLayer(ctypes.Structure):
     ]
 
 
+class NfxNafLayerGrad(ctypes.Structure):
+    """Mirror of `NfxNafLayerGrad` in include/nfx.h (device pointers of one DeepMADE layer's gradients)."""
+    _fields_ = [
+        ("weight", ctypes.c_void_p),
+        ("bias", ctypes.c_void_p),
+        ("ln_weight", ctypes.c_void_p),
+        ("ln_bias", ctypes.c_void_p),
+    ]
+
+
 _vp = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _int = ctypes.c_int
@@ -175,6 +185,13 @@ _SIGNATURES = {
     "nfx_naf_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
     "nfx_naf_pack": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "nfx_naf_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _f, _f, _int, _int, _vp]),
+    "nfx_naf_backward_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
+    "nfx_naf_backward_packed_floats": (_sz, [_int, _int, _vp]),
+    "nfx_naf_pack_backward": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+    "nfx_naf_backward_slots": (_sz, [_i64, _int, _int, _vp]),
+    "nfx_naf_backward_block_threads": (_sz, [_i64, _int, _int, _vp]),
+    "nfx_naf_backward_workspace_floats": (_sz, [_i64, _int, _int, _vp]),
+    "nfx_naf_backward": (_int, [_vp] * 8 + [_i64, _int, _int, _vp, _int, _int, _f, _f, _vp]),
     "nfx_rqs_unit": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int,
                                      _vp]),
@@ -245,7 +262,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
     "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
-    "nfx_made_sample_supported", "nfx_residual_supported", "nfx_naf_supported"))
+    "nfx_made_sample_supported", "nfx_residual_supported", "nfx_naf_supported", "nfx_naf_backward_supported"))
 
 
 _as_pointer = _vp.from_param  # (an int as a full-width pointer argument, without a c_void_p object)

@@ -25,7 +25,13 @@ never uses the masks to skip work across passes.
 Routing: CPU or fp64 tensors run the composite (`_torch_call`, the reference's operations in the
 reference's order, any dtype). Train mode with dropout > 0 runs the composite; LayerNorm has no
 train / eval difference, so train mode with dropout == 0 runs the kernel. Gradients recompute
-through the composite. The kernel family is 1 <= dim <= 16, 1 to 4 hidden layers of width 1..128
+through the composite by default; with `NeuralAutoregressiveFlow.fused_backward = True` (on the
+class or an instance) the gradients of `inverse`, the direction an NLL step uses, come from the
+fused reverse sweep (csrc/nfx_naf_bwd*.hip: the conditioner recomputed from x, the sweep, a
+fixed-order reduction) for hidden widths up to 64, in HIP only; wider layers and `forward` keep the
+composite route. Double backward is not supported there. A row with a non-finite input element or
+conditioner output adds nothing to any parameter gradient there and gets a zero input gradient,
+where autograd on the composite gives NaN (0 * NaN behind torch.where). The kernel family is 1 <= dim <= 16, 1 to 4 hidden layers of width 1..128
 whose packed image fits the LDS of one workgroup (nfx_naf_supported decides), relu / elu /
 leaky_relu(0.1) / gelu; the constructor's default [512, 512, 512] is outside it and raises
 NotImplementedError on the GPU (or runs the composite with ALLOW_TORCH_FALLBACK).
@@ -220,6 +226,10 @@ class NeuralAutoregressiveFlow(HipFlow):
     """Neural autoregressive flow (neural_autoregressive_flow.py:242-391); see the module docstring
     for the reference's quirk that this class mirrors."""
 
+    # True: the gradients of `inverse` come from the fused backward kernels (csrc/nfx_naf_bwd*.hip) for
+    # 1 to 4 hidden layers of width 1..64; False (the default) recomputes through the composite on the GPU.
+    fused_backward = False
+
     def __init__(self, dim, hidden_dims=[512, 512, 512], activation="relu", use_layer_norm=True, use_residual=True,
                  dropout=0.1, clamp_alpha=3.0, clamp_log_scale=5.0):
         super().__init__()
@@ -330,21 +340,9 @@ class NeuralAutoregressiveFlow(HipFlow):
     def _build_pack(self, device):
         L = _lib.checked()
         plan = self._plan()
-        hidden, out = plan[0], plan[1]
+        hidden = plan[0]
         widths, widths_ptr = self._widths_arg(plan)
-        keep = []
-
-        def p(t):
-            t = _lib.dense(t.detach().to(device=device, dtype=torch.float32))
-            keep.append(t)
-            return t.data_ptr()
-
-        raw = (_lib.NfxNafLayer * (len(hidden) + 1))()
-        for r, (lin, ln, _, res) in zip(raw, list(hidden) + [(out, None, None, False)]):
-            r.weight, r.bias, r.mask = p(lin.weight), p(lin.bias), p(lin.mask)
-            if ln is not None:
-                r.ln_weight, r.ln_bias, r.ln_eps = p(ln.weight), p(ln.bias), float(ln.eps)
-            r.residual = int(res)
+        raw, keep = self._raw_layers(device)
         packed = torch.empty(L.nfx_naf_packed_floats(self.dim, len(hidden), widths_ptr), device=device,
                              dtype=torch.float32)
         L.nfx_naf_pack(ctypes.addressof(raw), self.dim, len(hidden), widths_ptr, packed, _lib.stream_of(packed))
@@ -359,3 +357,107 @@ class NeuralAutoregressiveFlow(HipFlow):
             packed, x, out, log_det, x.shape[0], self.dim, len(hidden), widths_ptr, activation_code(hidden[0][2]), flags,
             float(self.clamp_alpha), float(self.clamp_log_scale),
             _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE, int(bool(accumulate)), _lib.stream_of(x))
+
+    # -- fused backward of the density direction (opt-in: NeuralAutoregressiveFlow.fused_backward = True) --
+    def _dispatch(self, x, direction):
+        if (self.fused_backward and direction < 0 and torch.is_grad_enabled() and self._route(x) == "hip"
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+                and self._hip_backward_ok(x)):
+            return _NafFunction.apply(self, x, *list(self.parameters()))
+        return super()._dispatch(x, direction)
+
+    def _hip_backward_ok(self, x, direction=-1):
+        """The fused backward is switched on and has kernels for this call (the density direction, 1 to
+        4 hidden layers of width 1..64); otherwise the gradients recompute through the composite."""
+        if not (self.fused_backward and direction < 0 and x.dim() == 2 and x.shape[1] == self.dim
+                and x.shape[0] >= 1):
+            return False
+        plan = self._plan()
+        if plan is None:
+            return False
+        keep, widths_ptr = self._widths_arg(plan)
+        return bool(_lib.lib().nfx_naf_backward_supported(x.shape[0], self.dim, len(plan[0]), widths_ptr,
+                                                          activation_code(plan[0][0][2]), plan[4]))
+
+    def _raw_layers(self, device):
+        """(NfxNafLayer array, the tensors it points to): the plan's layers as the C entry points read them."""
+        hidden, out = self._plan()[:2]
+        keep = []
+
+        def p(t):
+            t = _lib.dense(t.detach().to(device=device, dtype=torch.float32))
+            keep.append(t)
+            return t.data_ptr()
+
+        raw = (_lib.NfxNafLayer * (len(hidden) + 1))()
+        for r, (lin, ln, _, res) in zip(raw, list(hidden) + [(out, None, None, False)]):
+            r.weight, r.bias, r.mask = p(lin.weight), p(lin.bias), p(lin.mask)
+            if ln is not None:
+                r.ln_weight, r.ln_bias, r.ln_eps = p(ln.weight), p(ln.bias), float(ln.eps)
+            r.residual = int(res)
+        return raw, keep
+
+    def _build_backward_pack(self, device):
+        L = _lib.checked()
+        plan = self._plan()
+        widths, widths_ptr = self._widths_arg(plan)
+        raw, keep = self._raw_layers(device)
+        packed = torch.empty(L.nfx_naf_backward_packed_floats(self.dim, len(plan[0]), widths_ptr), device=device,
+                             dtype=torch.float32)
+        L.nfx_naf_pack_backward(ctypes.addressof(raw), self.dim, len(plan[0]), widths_ptr, packed,
+                                _lib.stream_of(packed))
+        return packed
+
+    def _hip_backward(self, x, gz, gld, direction=-1):
+        """(gx, one gradient per entry of list(self.parameters())) of the density direction, in HIP only."""
+        L = _lib.checked()
+        x = _lib.dense(x)
+        B, d = x.shape[0], self.dim
+        plan = self._plan()
+        hidden, out, _, _, flags = plan
+        widths, widths_ptr = self._widths_arg(plan)
+        packed = self._packed(x.device, self._build_backward_pack, slot="_nfx_bwd_pack_cache")
+        raw, keep = self._raw_layers(x.device)
+        gz = _lib.dense(gz.to(torch.float32))
+        gld = _lib.dense(gld.to(torch.float32))
+        gx = torch.empty_like(x)
+        by_param = {}
+        grads = (_lib.NfxNafLayerGrad * (len(hidden) + 1))()
+        for g, (lin, ln, _, _) in zip(grads, list(hidden) + [(out, None, None, False)]):
+            for name, p in (("weight", lin.weight), ("bias", lin.bias)) + (
+                    () if ln is None else (("ln_weight", ln.weight), ("ln_bias", ln.bias))):
+                t = torch.empty(p.shape, device=x.device, dtype=torch.float32)
+                by_param[id(p)] = t
+                setattr(g, name, t.data_ptr())
+        ws = torch.empty(L.nfx_naf_backward_workspace_floats(B, d, len(hidden), widths_ptr), device=x.device,
+                         dtype=torch.float32)
+        L.nfx_naf_backward(packed, ctypes.addressof(raw), x, gz, gld, gx, ctypes.addressof(grads), ws, B, d,
+                           len(hidden), widths_ptr, activation_code(hidden[0][2]), flags, float(self.clamp_alpha),
+                           float(self.clamp_log_scale), _lib.stream_of(x))
+        return gx, [by_param[id(p)] for p in self.parameters()]
+
+
+class _NafFunction(torch.autograd.Function):
+    """NeuralAutoregressiveFlow.inverse with the fused backward: the forward kernel as it stands (only
+    the dense x is saved), then the reverse sweep in HIP. No composite anywhere; double backward is
+    not supported."""
+
+    @staticmethod
+    def forward(ctx, layer, x, *params):
+        x = _lib.dense(x)  # (saved in this form: a strided or offset input is copied once, not per pass)
+        with torch.no_grad():
+            y, ld = layer._hip_call(x.detach(), -1)  # (counts STATS["hip"])
+        ctx.layer = layer
+        ctx.save_for_backward(x)
+        return y, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gz, gld):
+        from . import flow as _flow
+        (x,) = ctx.saved_tensors
+        layer = ctx.layer
+        _flow.STATS["hip"] += 1
+        gx, gparams = layer._hip_backward(x.detach(), gz, gld)
+        gparams = [g if p.requires_grad else None for p, g in zip(layer.parameters(), gparams)]
+        return (None, gx, *gparams)

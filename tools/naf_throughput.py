@@ -16,6 +16,15 @@ call outside the kernel family runs under ALLOW_TORCH_FALLBACK, and the only thi
 user can run): one conditioner call for the inverse, `dim` of them for the forward. The weights are
 redrawn at Xavier gain 2, so the +-2 clamp of the conditioner is reached. The fused call must be the
 faster one in every cell (`all_faster`, and the exit status). Prints one JSON line.
+
+    python tools/naf_throughput.py --train [--batches 1024,65536] [--replays 20] [--calls 20] [--out FILE.json]
+
+`--train` times one NLL step instead, `NormalizingFlowModel([flow]).log_prob(x).mean().backward()` with
+the optimizer left out, for (4, [64, 64]) and (16, [64, 64]): the fused backward
+(`NeuralAutoregressiveFlow.fused_backward = True`, no composite call) against the composite-recompute
+route (the flag off: the fused forward kernel, then the eager DeepMADE and autograd), the same windows
+taken in turn, `--calls` steps per window on both routes. The fused step's slowest window must lie
+below the composite route's fastest in every cell (`all_below`, and the exit status).
 """
 import argparse
 import copy
@@ -74,6 +83,56 @@ def time_alternating(fused, eager, warmup, replays, calls, eager_calls):
     return ms, ems
 
 
+TRAIN_MODELS = [(4, [64, 64]), (16, [64, 64])]
+
+
+def train(a, dev):
+    """One NLL step per call: the fused backward against the composite recompute."""
+    rows = []
+    for d, hidden in TRAIN_MODELS:
+        flow = make_flow(d, hidden, a.activation, dev)
+        plain = nfs_amd.NormalizingFlowModel([copy.deepcopy(flow)]).to(dev)
+        flow.fused_backward = True
+        fused = nfs_amd.NormalizingFlowModel([flow]).to(dev)
+        for B in [int(b) for b in a.batches.split(",")]:
+            x = 1.5 * torch.randn(B, d, generator=torch.Generator().manual_seed(B)).to(dev)
+
+            def step(model):
+                model.zero_grad(set_to_none=True)
+                (-model.log_prob(x).mean()).backward()
+
+            nfs_amd.reset_stats()
+            step(fused)
+            assert nfs_amd.STATS["torch"] == 0 and nfs_amd.STATS["hip"] >= 2, nfs_amd.STATS
+            nfs_amd.reset_stats()
+            step(plain)
+            assert nfs_amd.STATS["torch"] == 1, nfs_amd.STATS
+            agree = max(float((p.grad - q.grad).abs().max() / q.grad.abs().max().clamp_min(1e-30))
+                        for p, q in zip(fused.parameters(), plain.parameters()))
+            for _ in range(a.warmup):
+                step(fused)
+                step(plain)
+            torch.cuda.synchronize()
+            ms, ems = [], []
+            for _ in range(a.replays):
+                ms.append(window(lambda: step(fused), a.calls))
+                ems.append(window(lambda: step(plain), a.calls))
+            med, emed = statistics.median(ms), statistics.median(ems)
+            rows.append({"dim": d, "hidden_dims": hidden, "B": B, "fused_ms_median": med, "fused_ms_min": min(ms),
+                         "fused_ms_max": max(ms), "composite_ms_median": emed, "composite_ms_min": min(ems),
+                         "composite_ms_max": max(ems), "fused_speedup_over_composite": emed / med,
+                         "fused_slowest_below_composite_fastest": max(ms) < min(ems),
+                         "max_relative_gradient_difference": agree})
+            print(f"[naf train] ({d}, {hidden}) B={B}: fused backward {med:.3f} ms (min {min(ms):.3f}, max "
+                  f"{max(ms):.3f}), composite recompute {emed:.3f} ms (min {min(ems):.3f}, max {max(ems):.3f}); fused is "
+                  f"{emed / med:.1f}x; gradients differ by {agree:.1e} relative", file=sys.stderr, flush=True)
+    res = {"models": [f"NeuralAutoregressiveFlow({d}, {h}, activation={a.activation!r})" for d, h in TRAIN_MODELS],
+           "workload": "one NLL step: (-NormalizingFlowModel([flow]).log_prob(x).mean()).backward(), no optimizer",
+           "device": torch.cuda.get_device_name(0), "replays": a.replays, "steps_per_window": a.calls,
+           "all_below": all(r["fused_slowest_below_composite_fastest"] for r in rows), "results": rows}
+    return res, res["all_below"]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batches", default="1024,65536")
@@ -83,8 +142,12 @@ def main():
     ap.add_argument("--eager-calls", type=int, default=5)
     ap.add_argument("--activation", default="relu")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--train", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.train:
+        res, ok = train(a, dev)
+        return finish(res, ok, a.out)
     rows = []
     for d, hidden in MODELS:
         flow = make_flow(d, hidden, a.activation, dev)
@@ -115,13 +178,17 @@ def main():
            "device": torch.cuda.get_device_name(0), "replays": a.replays, "calls_per_window": a.calls,
            "eager_calls_per_window": a.eager_calls,
            "all_faster": all(r["fused_ms_median"] < r["eager_ms_median"] for r in rows), "results": rows}
+    return finish(res, res["all_faster"], a.out)
+
+
+def finish(res, ok, out):
     line = json.dumps(res)
     print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
             f.write(line + "\n")
-    return 0 if res["all_faster"] else 1
+    return 0 if ok else 1
 
 
 if __name__ == "__main__":
