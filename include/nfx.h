@@ -844,6 +844,49 @@ int nfx_naf_backward(const float* packed, const NfxNafLayer* layers, const float
                      int n_hidden, const int* widths, int activation, int flags, float clamp_alpha,
                      float clamp_log_scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * PlanarFlow, RadialFlow, SylvesterFlow (src/flows/advanced/planar_flow.py, radial_flow.py,
+ * sylvester_flow.py): a stack of n_layers layers of any mix of the three kinds at one dim, in one
+ * launch (lowrank_stack_kernel), one lane per sample, z in registers from load to store.
+ *   Planar     z + u tanh(w.z + b),                     log(|1 + u.w psi| + 1e-8), psi = 1 - tanh^2
+ *   Radial     z + beta h (z - z0), h = 1 / (alpha + r + 1e-8), r = |z - z0|,
+ *              (dim - 1) log(|1 + beta h| + 1e-8) + log(|1 + beta h + beta h' r| + 1e-8),
+ *              h' = -1 / ((alpha + r)^2 + 1e-8)
+ *   Sylvester  z + Bm tanh(A z + b), A = R Qm, Bm = Qm R^T, Qm = H_K ... H_1;
+ *              log(|det(I + R R^T diag(psi))| + 1e-8): the reference's formula, whatever the true
+ *              Jacobian is
+ * A NaN / Inf log-det becomes 0; the values have no guard.
+ * The image is n_layers records of nfx_lowrank_record_floats(dim) floats each (the same size for
+ * every kind; 0 outside the family); layer i is record i. The pack entries write one record on the
+ * device (one launch each, float64 sums rounded to fp32, nothing read back):
+ *   nfx_lowrank_pack_planar     w [dim], u_hat [dim], b [1]: the constrained u and u.w
+ *   nfx_lowrank_pack_radial     z0 [dim], alpha_hat [1], beta_hat [1]: alpha = softplus(alpha_hat),
+ *                               beta = -alpha + softplus(beta_hat)
+ *   nfx_lowrank_pack_sylvester  v [num_householder, dim] (the reflection vectors in list order),
+ *                               R [num_transforms, dim], b [num_transforms]: A, Bm, R R^T, b
+ * max_iter and tol are the layer's fixed-point constants, kept in its record.
+ *   nfx_lowrank_stack   NFX_FORWARD: the layers in order. NFX_INVERSE: the layers in reversed order,
+ *                       each as z <- x - g(z) from z = x, at most max_iter times; a sample stops when
+ *                       its OWN ||z_new - z||_2 < tol and keeps z, the iterate before that step (one
+ *                       that reaches max_iter keeps its last z_new); its log-det is minus the
+ *                       forward formula at z. A row's result does not depend on the other rows.
+ *                       log_det = (accumulate ? log_det : 0) + ld_0 + ld_1 + ... in float32, in the
+ *                       order the layers run.
+ * Kernel family: 1 <= dim <= 64, 1 <= n_layers <= 256, num_transforms <= 8, 0 <= max_iter <= 1000,
+ * any B >= 1 (nfx_lowrank_supported: 1 inside it, host-only check); NFX_EUNSUPPORTED elsewhere.
+ * B == 0 is a no-op. x and out must not alias.
+ * ------------------------------------------------------------------------------------- */
+int nfx_lowrank_supported(int64_t B, int dim, int n_layers);
+size_t nfx_lowrank_record_floats(int dim);
+int nfx_lowrank_pack_planar(const float* w, const float* u_hat, const float* b, int dim, int max_iter, float tol,
+                            float* record, void* stream);
+int nfx_lowrank_pack_radial(const float* z0, const float* alpha_hat, const float* beta_hat, int dim, int max_iter,
+                            float tol, float* record, void* stream);
+int nfx_lowrank_pack_sylvester(const float* v, const float* R, const float* b, int dim, int num_householder,
+                               int num_transforms, int max_iter, float tol, float* record, void* stream);
+int nfx_lowrank_stack(const float* image, int n_layers, const float* x, float* out, float* log_det, int64_t B,
+                      int dim, int direction, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,12 +7,14 @@ from . import _lib
 from .flows import (Flow, SequentialFlow, CouplingLayer, SplineCouplingLayer,
                     rational_quadratic_spline, ARQS, MaskedLinear, MADE, MaskedAutoregressiveFlow,
                     InverseAutoregressiveFlow, made_degrees, ODEFunc, ContinuousFlow, SpectralNorm, ResidualBlock,
-                    ResidualFlow, DeepMADE, NeuralAutoregressiveFlow, STATS, reset_stats)
+                    ResidualFlow, DeepMADE, NeuralAutoregressiveFlow, PlanarFlow, RadialFlow, HouseholderReflection,
+                    OrthogonalMatrix, SylvesterFlow, STATS, reset_stats)
 from .models import NormalizingFlowModel, RealNVP, RealNVPSpline, gauss_logprob
 from .graphs import GraphedFlow, GraphedTrainStep
 
 __all__ = ["Flow", "SequentialFlow", "CouplingLayer", "SplineCouplingLayer",
            "rational_quadratic_spline", "ARQS", "MaskedLinear", "MADE", "MaskedAutoregressiveFlow",
            "InverseAutoregressiveFlow", "ODEFunc", "ContinuousFlow", "SpectralNorm", "ResidualBlock",
-           "ResidualFlow", "DeepMADE", "NeuralAutoregressiveFlow", "NormalizingFlowModel", "RealNVP", "RealNVPSpline",
+           "ResidualFlow", "DeepMADE", "NeuralAutoregressiveFlow", "PlanarFlow", "RadialFlow", "HouseholderReflection",
+           "OrthogonalMatrix", "SylvesterFlow", "NormalizingFlowModel", "RealNVP", "RealNVPSpline",
            "gauss_logprob", "made_degrees", "STATS", "reset_stats", "GraphedFlow", "GraphedTrainStep"]

@@ -8,9 +8,11 @@ from .autoregressive import (MaskedLinear, MADE, MaskedAutoregressiveFlow,
 from .continuous import ODEFunc, ContinuousFlow
 from .residual import SpectralNorm, ResidualBlock, ResidualFlow
 from .naf import DeepMADE, NeuralAutoregressiveFlow
+from .lowrank import PlanarFlow, RadialFlow, HouseholderReflection, OrthogonalMatrix, SylvesterFlow
 
 __all__ = ["Flow", "SequentialFlow", "HipFlow", "CouplingLayer", "SplineCouplingLayer",
            "rational_quadratic_spline", "ARQS", "MaskedLinear", "MADE", "MaskedAutoregressiveFlow",
            "InverseAutoregressiveFlow", "made_degrees", "ODEFunc", "ContinuousFlow", "SpectralNorm", "ResidualBlock",
-           "ResidualFlow", "DeepMADE", "NeuralAutoregressiveFlow", "STATS", "reset_stats", "drop_pack_caches",
+           "ResidualFlow", "DeepMADE", "NeuralAutoregressiveFlow", "PlanarFlow", "RadialFlow", "HouseholderReflection",
+           "OrthogonalMatrix", "SylvesterFlow", "STATS", "reset_stats", "drop_pack_caches",
            "drop_layer_pack_caches"]

@@ -245,6 +245,8 @@ def drop_pack_caches(module):
     for m in module.modules():
         if isinstance(m, HipFlow):
             drop_layer_pack_caches(m)
+        else:  # a container's image of a Planar / Radial / Sylvester stack (lowrank._stack_image)
+            m.__dict__.pop("_nfx_lowrank_pack_cache", None)
 
 
 def drop_layer_pack_caches(layer):
@@ -296,11 +298,16 @@ class SequentialFlow(Flow):
         x = _lib.dense(x)
         ld = torch.zeros(x.shape[0], device=x.device, dtype=torch.float32)
         from . import coupling as _coupling
+        from . import lowrank as _lowrank
         from . import spline as _spline
-        for mod in (_coupling, _spline):  # one launch (csrc/nfx_affine_*chain*, nfx_spline_schain*)
+        # one launch (csrc/nfx_affine_*chain*, nfx_spline_schain*, nfx_lowrank*)
+        for mod in (_coupling, _spline, _lowrank):
             if mod.chain_ok(list(self.flows), x):
                 out = torch.empty_like(x)
-                mod.chain_launch(list(self.flows), x, out, ld, direction, True)
+                if mod is _lowrank:
+                    mod.chain_launch(list(self.flows), x, out, ld, direction, True, owner=self)
+                else:
+                    mod.chain_launch(list(self.flows), x, out, ld, direction, True)
                 return out, ld
         bufs = [torch.empty_like(x), torch.empty_like(x)]
         cur, k = x, 0

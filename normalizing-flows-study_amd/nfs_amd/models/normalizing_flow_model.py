@@ -21,6 +21,7 @@ from .. import _lib
 from ..distributed import merge_bn_stats, sync_bn_world
 from ..flows import autoregressive as _autoregressive
 from ..flows import coupling as _coupling
+from ..flows import lowrank as _lowrank
 from ..flows import spline as _spline
 from ..flows.flow import HipFlow, STATS
 
@@ -134,20 +135,23 @@ class NormalizingFlowModel(nn.Module):
         n = len(self.flows)
         chain = None
         if not self.batch_norm_between_layers:
-            chain = next((m for m in (_coupling, _spline) if m.chain_ok(list(self.flows), x)), None)
+            chain = next((m for m in (_coupling, _spline, _lowrank) if m.chain_ok(list(self.flows), x)), None)
         if chain is not None:
             # the whole chain in one launch (csrc/nfx_affine_chain.hip / nfx_affine_schain.hip /
-            # nfx_spline_schain_kernel.h), the per-layer kernels' roundings
+            # nfx_spline_schain_kernel.h / nfx_lowrank_kernel.h), the per-layer kernels' roundings
             out = torch.empty_like(x)
             ev = self.layer_events
             if ev is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-            chain.chain_launch(list(self.flows), x, out, ld, direction, False, logprob)
+            if chain is _lowrank:  # (no fused log-density: the caller runs nfx_gauss_logprob)
+                chain.chain_launch(list(self.flows), x, out, ld, direction, False, owner=self)
+            else:
+                chain.chain_launch(list(self.flows), x, out, ld, direction, False, logprob)
             if ev is not None:
                 e1.record()
                 ev.append((_lib.last_kernel(), e0, e1))
-            return (out, ld, True) if logprob is not None else (out, ld)
+            return (out, ld, chain is not _lowrank) if logprob is not None else (out, ld)
         bufs = [torch.empty_like(x), torch.empty_like(x)]
         order = range(n) if direction > 0 else reversed(range(n))
         cur, k, first, fused = x, 0, True, False
