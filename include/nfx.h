@@ -887,6 +887,45 @@ int nfx_lowrank_pack_sylvester(const float* v, const float* R, const float* b, i
 int nfx_lowrank_stack(const float* image, int n_layers, const float* x, float* out, float* log_det, int64_t B,
                       int dim, int direction, int accumulate, void* stream);
 
+/* Fused backward of the stack above (lowrank_bwd_kernel, csrc/nfx_lowrank_bwd*.hip): the gradients of
+ * <gv, values> + <gld, log_det> with respect to the input and, through the record entries, every
+ * parameter. One lane per row, z and its cotangent in registers for the whole stack.
+ *   NFX_FORWARD  one layer (n_layers == 1); `point` is the layer's input.
+ *   NFX_INVERSE  a stack of up to nfx_lrbwd_max_layers(dim) layers; `point` is the stack's OUTPUT z, the
+ *                only thing the forward saves. The sweep visits the layers first to last; after layer l
+ *                z + g_l(z) is the next layer's output. Each layer contributes the implicit-function
+ *                gradient at the returned z, x_bar = (I + J_g)^-T (z_bar - l_bar dld/dz): the gradient
+ *                of the function the fixed-point iteration approximates, not of its unrolled steps
+ *                (closed rank-one solve for Planar and Radial; for Sylvester the adjoint iteration
+ *                with the layer's max_iter and a per-row stop at a step of norm tol |rhs|, relative, so
+ *                that gradients scale with the cotangents).
+ * A row with a non-finite point, cotangent or coefficient at some layer adds nothing to that layer's
+ * and the later layers' parameter gradients and gets gx = 0 (autograd gives NaN there).
+ * The reduction over rows uses no float atomics: workgroup g (one wave) owns the
+ * nfx_lrbwd_chunk_rows-row chunks g, g + G, ... with G = nfx_lrbwd_slots(B, ...) (capped, so the
+ * workspace is bounded whatever B), keeps the stack's gradient image in LDS (this sets
+ * nfx_lrbwd_max_layers: image + staging within 160 KiB) and writes it once; lowrank_bwd_reduce_kernel
+ * adds the images in order into float64 totals. The same inputs give the same bits.
+ *   nfx_lrbwd_supported         host-only: 1 inside the family above, else 0
+ *   nfx_lrbwd_workspace_floats  floats of `workspace` (8-byte aligned, any content on entry); 0 outside
+ *   nfx_lrbwd_stack             two launches; gx [B, dim] must alias neither point nor gv; B == 0 no-op
+ *   nfx_lrbwd_param_grads       after nfx_lrbwd_stack with the same (workspace, B, dim, n_layers): the
+ *                               adjoint of layer `layer`'s pack kernel, one 64-thread workgroup, sums in
+ *                               float64, written in the parameters' own layout; a NULL output is not
+ *                               written. kind 0 Planar (p = w, u_hat, b), 1 Radial (z0, alpha_hat,
+ *                               beta_hat), 2 Sylvester (v [num_householder, dim], R, b).
+ * ------------------------------------------------------------------------------------- */
+int nfx_lrbwd_supported(int64_t B, int dim, int n_layers, int direction);
+size_t nfx_lrbwd_max_layers(int dim);
+size_t nfx_lrbwd_chunk_rows(int dim);
+size_t nfx_lrbwd_slots(int64_t B, int dim, int n_layers);
+size_t nfx_lrbwd_workspace_floats(int64_t B, int dim, int n_layers);
+int nfx_lrbwd_stack(const float* image, int n_layers, const float* point, const float* gv, const float* gld, float* gx,
+                    float* workspace, int64_t B, int dim, int direction, void* stream);
+int nfx_lrbwd_param_grads(const float* workspace, int64_t B, int dim, int n_layers, int layer, int kind,
+                          const float* p0, const float* p1, const float* p2, float* g0, float* g1, float* g2,
+                          int num_householder, int num_transforms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

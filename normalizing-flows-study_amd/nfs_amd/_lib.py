@@ -198,6 +198,13 @@ _SIGNATURES = {
     "nfx_lowrank_pack_radial": (_int, [_vp, _vp, _vp, _int, _int, _f, _vp, _vp]),
     "nfx_lowrank_pack_sylvester": (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _f, _vp, _vp]),
     "nfx_lowrank_stack": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _int, _int, _int, _vp]),
+    "nfx_lrbwd_supported": (_int, [_i64, _int, _int, _int]),
+    "nfx_lrbwd_max_layers": (_sz, [_int]),
+    "nfx_lrbwd_chunk_rows": (_sz, [_int]),
+    "nfx_lrbwd_slots": (_sz, [_i64, _int, _int]),
+    "nfx_lrbwd_workspace_floats": (_sz, [_i64, _int, _int]),
+    "nfx_lrbwd_stack": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _vp]),
+    "nfx_lrbwd_param_grads": (_int, [_vp, _i64, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp]),
     "nfx_rqs_unit": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int, _vp]),
     "nfx_rqs_unit_backward": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _f, _f, _f, _int,
                                      _vp]),
@@ -269,7 +276,7 @@ _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
     "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
     "nfx_made_sample_supported", "nfx_residual_supported", "nfx_naf_supported", "nfx_naf_backward_supported",
-    "nfx_lowrank_supported"))
+    "nfx_lowrank_supported", "nfx_lrbwd_supported"))
 
 
 _as_pointer = _vp.from_param  # (an int as a full-width pointer argument, without a c_void_p object)

@@ -8,7 +8,9 @@ Routing (HipFlow._route):
   * fp32 tensors on a ROCm device  -> the layer's fused gfx950 kernel through libnfx.so.
     If autograd needs gradients, the kernel still computes the outputs and HipFlowFunction's
     backward runs the layer's fused backward kernels (`_hip_backward`: MADE flows in every
-    direction, spline coupling, eval-mode affine coupling); shapes outside those kernel
+    direction, spline coupling, eval-mode affine coupling; Planar / Radial / Sylvester layers with
+    `fused_backward = True`, a stack of which runs its `inverse` as one launch each way under
+    grad, flows/lowrank.py); shapes outside those kernel
     families recompute through the layer's torch composite on the GPU.
   * CPU tensors or fp64 (gradcheck)  -> the layer's torch composite (same math as the reference).
   * train-mode BatchNorm in a conditioner (CouplingLayer) -> the train-mode kernels
@@ -281,6 +283,9 @@ class SequentialFlow(Flow):
     def inverse(self, x):
         if self._hip_chain_ok(x):
             return self._hip_chain(x, -1)
+        from . import lowrank as _lowrank
+        if _lowrank.fused_stack_ok(list(self.flows), x):  # under grad: one launch each way
+            return _lowrank.fused_stack_inverse(list(self.flows), x, owner=self)
         total_log_det = torch.zeros(x.size(0), device=x.device)
         for flow in reversed(self.flows):
             x, log_det = flow.inverse(x)

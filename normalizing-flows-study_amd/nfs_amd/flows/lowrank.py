@@ -22,8 +22,24 @@ row the two rules are the same.
 
 The gfx950 path is one kernel for all three kinds (csrc/nfx_lowrank*.hip): a stack of layers at one
 dim in one launch, a single layer being a stack of one. Family: dim <= 64, num_transforms <= 8,
-max_iter <= 1000, at most 256 layers. Gradients recompute through the composite
-(HipFlowFunction's recompute route, counted in STATS["torch"]): there is no fused backward yet.
+max_iter <= 1000, at most 256 layers. Gradients recompute through the composite by default
+(HipFlowFunction's recompute route, counted in STATS["torch"]).
+
+With `fused_backward = True` (on a class or an instance, default off) the gradients come from the fused
+backward (csrc/nfx_lowrank_bwd*.hip), in HIP only, in train and eval mode alike: a single layer in
+either direction, and the `inverse` (so log_prob and nll) of a SequentialFlow or NormalizingFlowModel
+made only of these layers at one dim, every one with the switch on and no between-layer BatchNorm, as ONE
+forward launch that saves only its output and ONE backward launch for the whole stack (up to
+`max_fused_backward_layers(dim)` layers, the LDS budget of the gradient accumulators; a longer stack, and
+`forward` under grad, run layer by layer, each layer with its own fused backward).
+ONE DELIBERATE DIFFERENCE there: the composite differentiates the unrolled fixed-point iteration; the
+fused backward of `inverse` returns the implicit-function gradient (I + J_g(z))^-T at the returned z,
+the gradient of the function the iteration approximates. The two differ by about K rho^K (rho the
+contraction, K the steps): measured in float64 between the own-settings unrolled gradient and the
+converged one, 5e-7 .. 2.8e-4 of max|grad| for single layers at bounds 0.31 and 0.6, 7e-4 for a
+five-layer mixed stack (tests/test_lowrank_backward_cpu.py prints it per case). A row with a non-finite z, cotangent or per-row coefficient adds nothing to the
+parameter gradients and gets a zero input gradient, where autograd on the composite gives NaN. Double
+backward is not supported there.
 """
 import torch
 import torch.nn as nn
@@ -53,8 +69,19 @@ def _guard(log_det):
     return torch.where(torch.isnan(log_det) | torch.isinf(log_det), torch.zeros_like(log_det), log_det)
 
 
+def max_fused_backward_layers(dim):
+    """Layers one fused stack backward takes at this dim: the stack's gradient image and the staging
+    of one wave must fit the LDS of a workgroup (nfx_lrbwd_max_layers)."""
+    return int(_lib.lib().nfx_lrbwd_max_layers(int(dim)))
+
+
 class _LowRankFlow(HipFlow):
     """What the three kinds share: the fixed-point inverse, the routing and the one-record pack."""
+
+    # True: gradients come from the fused backward kernels (csrc/nfx_lowrank_bwd*.hip) instead of a
+    # recompute through the composite; see the module docstring for the implicit-gradient difference.
+    fused_backward = False
+    _KIND = None  # the record's kind code (csrc/nfx_lowrank_kernel.h)
 
     def _init_common(self, dim):
         self.data_dim = dim
@@ -112,6 +139,53 @@ class _LowRankFlow(HipFlow):
                                          _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE,
                                          int(bool(accumulate)), _lib.stream_of(x))
 
+    # -- fused backward (opt-in: fused_backward = True) ---------------------------------------------
+    def _dispatch(self, x, direction):
+        if (self.fused_backward and torch.is_grad_enabled() and self._route(x) == "hip"
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+                and self._hip_backward_ok(x, direction)):
+            return _LowRankFunction.apply((self,), None, direction, x, *list(self.parameters()))
+        return super()._dispatch(x, direction)
+
+    def _hip_backward_ok(self, x, direction=-1):
+        """The fused backward is switched on and has a kernel for this call."""
+        if not (self.fused_backward and x.dim() == 2 and x.shape[1] == self.dim and x.shape[0] >= 1):
+            return False
+        if x.device.type != "cuda" or x.dtype != torch.float32 or self._family_reason():
+            return False
+        return bool(_lib.lib().nfx_lrbwd_supported(x.shape[0], self.dim, 1,
+                                                   _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE))
+
+    def _hip_backward(self, x, gy, gld, direction=-1):
+        """HipFlowFunction's hook: (gx, one gradient per entry of list(self.parameters())) from the
+        layer's INPUT x. The inverse's Jacobian is taken at its output, which the forward kernel
+        computes again here (_LowRankFunction, the route `_dispatch` takes, saves it instead)."""
+        x = _lib.dense(x)
+        point = x if direction > 0 else self._hip_call(x, -1)[0]
+        record = self._packed(x.device, self._build_pack)
+        gx, grads = _stack_backward((self,), record, point, gy, gld, direction)
+        return gx, grads
+
+    def _param_tensors(self, device):
+        """(p0, p1, p2, num_householder, num_transforms, [(parameter, gradient slot)]) of
+        nfx_lrbwd_param_grads: the parameters as the pack reads them and which output is whose."""
+        raise NotImplementedError
+
+    def _param_grads(self, ws, B, n_layers, layer):
+        """This layer's parameter gradients from the reduced record gradients in `ws`, in
+        list(self.parameters()) order; no launch when no parameter needs one."""
+        params = list(self.parameters())
+        if not any(p.requires_grad for p in params):
+            return [None] * len(params)
+        p0, p1, p2, nh, nt, shapes = self._param_tensors(ws.device)
+        outs = [torch.empty(shape, device=ws.device, dtype=torch.float32) for shape in shapes]
+        _lib.checked().nfx_lrbwd_param_grads(ws, B, self.dim, n_layers, layer, self._KIND, p0, p1, p2, outs[0], outs[1],
+                                             outs[2], nh, nt, _lib.stream_of(ws))
+        return self._grads_in_order(outs)
+
+    def _grads_in_order(self, outs):
+        return outs
+
 
 class PlanarFlow(_LowRankFlow):
     """Planar flow (planar_flow.py): z + u tanh(w.z + b)."""
@@ -152,6 +226,12 @@ class PlanarFlow(_LowRankFlow):
             return x + g(x), self._log_det(x, u, w, b)
         z = self._fixed_point(x, g)
         return z, -self._log_det(z, u, w, b)
+
+    _KIND = 0
+
+    def _param_tensors(self, device):
+        return (self._dev(self.w, device), self._dev(self.u_hat, device), self._dev(self.b, device), 0, 0,
+                [self.w.shape, self.u_hat.shape, self.b.shape])
 
     def _pack_record(self, record, device):
         _lib.checked().nfx_lowrank_pack_planar(self._dev(self.w, device), self._dev(self.u_hat, device),
@@ -205,6 +285,12 @@ class RadialFlow(_LowRankFlow):
             return x + g(x), self._log_det(x, z0, alpha, beta)
         z = self._fixed_point(x, g)
         return z, -self._log_det(z, z0, alpha, beta)
+
+    _KIND = 1
+
+    def _param_tensors(self, device):
+        return (self._dev(self.z0, device), self._dev(self.alpha_hat, device), self._dev(self.beta_hat, device), 0, 0,
+                [self.z0.shape, self.alpha_hat.shape, self.beta_hat.shape])
 
     def _pack_record(self, record, device):
         _lib.checked().nfx_lowrank_pack_radial(self._dev(self.z0, device), self._dev(self.alpha_hat, device),
@@ -319,6 +405,21 @@ class SylvesterFlow(_LowRankFlow):
             why = f"num_transforms={self.num_transforms} outside 1..{MAX_TRANSFORMS}"
         return why
 
+    _KIND = 2
+
+    def _param_tensors(self, device):
+        refl = list(self.Q.reflections)
+        v = torch.stack([self._dev(r.v, device) for r in refl]) if refl else None
+        return (v, self._dev(self.R, device), self._dev(self.b, device), len(refl), self.num_transforms,
+                [(max(len(refl), 1), self.dim), self.R.shape, self.b.shape])
+
+    def _grads_in_order(self, outs):
+        gv, gR, gb = outs
+        by_param = {id(self.R): gR, id(self.b): gb}
+        for k, r in enumerate(self.Q.reflections):
+            by_param[id(r.v)] = gv[k]
+        return [by_param[id(p)] for p in self.parameters()]
+
     def _pack_record(self, record, device):
         refl = list(self.Q.reflections)
         v = torch.stack([self._dev(r.v, device) for r in refl]) if refl else None
@@ -369,3 +470,74 @@ def chain_launch(flows, x, out, ld, direction, accumulate, owner=None):
                                      _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE, int(bool(accumulate)),
                                      _lib.stream_of(x))
     STATS["hip"] += 1
+
+
+# ---- the fused backward: one layer in either direction, or a whole stack's inverse -----------------
+def _stack_backward(flows, image, point, gv, gld, direction):
+    """(gx, [one gradient per parameter of every layer, in order]) from one nfx_lrbwd_stack launch (and
+    its fixed-order reduction), then one nfx_lrbwd_param_grads launch per layer. HIP only."""
+    L = _lib.checked()
+    B, dim, n = point.shape[0], flows[0].dim, len(flows)
+    gv = _lib.dense(gv.to(torch.float32))
+    gld = _lib.dense(gld.to(torch.float32))
+    gx = torch.empty_like(point)
+    ws = torch.empty(L.nfx_lrbwd_workspace_floats(B, dim, n), device=point.device, dtype=torch.float32)
+    L.nfx_lrbwd_stack(image, n, point, gv, gld, gx, ws, B, dim,
+                      _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE, _lib.stream_of(point))
+    grads = []
+    for i, f in enumerate(flows):
+        grads += f._param_grads(ws, B, n, i)
+    return gx, grads
+
+
+class _LowRankFunction(torch.autograd.Function):
+    """`flows` (one layer, either direction; or a stack, inverse only) with the fused backward: the
+    forward kernel as it stands in one launch, saving the point the Jacobian is taken at (the input
+    for forward, the OUTPUT z for inverse), then the sweep in HIP. No composite anywhere; double
+    backward is not supported."""
+
+    @staticmethod
+    def forward(ctx, flows, owner, direction, x, *params):
+        x = _lib.dense(x)
+        with torch.no_grad():
+            if len(flows) == 1:
+                y, ld = flows[0]._hip_call(x.detach(), direction)  # (counts STATS["hip"])
+            else:
+                y = torch.empty_like(x)
+                ld = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
+                chain_launch(list(flows), x.detach(), y, ld, direction, False, owner=owner)
+        ctx.flows, ctx.owner, ctx.direction = flows, owner, direction
+        ctx.save_for_backward(x if direction > 0 else y)
+        return y, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, gld):
+        (point,) = ctx.saved_tensors
+        flows = ctx.flows
+        STATS["hip"] += 1
+        if len(flows) == 1:
+            image = flows[0]._packed(point.device, flows[0]._build_pack)
+        else:
+            image = _stack_image(list(flows), point.device, ctx.owner)
+        gx, grads = _stack_backward(flows, image, point.detach(), gy, gld, ctx.direction)
+        params = [p for f in flows for p in f.parameters()]
+        grads = [g if p.requires_grad else None for p, g in zip(params, grads)]
+        return (None, None, None, gx, *grads)
+
+
+def fused_stack_ok(flows, x):
+    """`inverse` of these layers under grad as one forward and one backward launch: every layer one
+    of the three kinds with the switch on, one dim, fp32 ROCm rows, within the backward's budget."""
+    if not torch.is_grad_enabled() or len(flows) < 2 or not chain_ok(flows, x) or x.shape[0] < 1:
+        return False
+    if not all(f.fused_backward for f in flows):
+        return False
+    if not (x.requires_grad or any(p.requires_grad for f in flows for p in f.parameters())):
+        return False
+    return bool(_lib.lib().nfx_lrbwd_supported(x.shape[0], x.shape[1], len(flows), _lib.NFX_INVERSE))
+
+
+def fused_stack_inverse(flows, x, owner=None):
+    """(z, log_det) of the stack's inverse with the one-launch fused backward behind it."""
+    return _LowRankFunction.apply(tuple(flows), owner, -1, x, *[p for f in flows for p in f.parameters()])

@@ -167,6 +167,8 @@ class GraphedTrainStep:
     def _forget(self):
         for m in self._hipflows:
             _flows.drop_layer_pack_caches(m)
+        for m in self.model.modules():  # a container's image of a Planar / Radial / Sylvester stack
+            m.__dict__.pop("_nfx_lowrank_pack_cache", None)
 
     def _step(self, zero=True):
         if zero:

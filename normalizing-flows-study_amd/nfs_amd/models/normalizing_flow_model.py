@@ -63,6 +63,9 @@ class NormalizingFlowModel(nn.Module):
     def inverse(self, x):
         if self._hip_chain_ok(x):
             return self._hip_chain(x, -1)
+        if not self.batch_norm_between_layers and _lowrank.fused_stack_ok(list(self.flows), x):
+            # Planar / Radial / Sylvester layers with fused_backward on, under grad: one launch each way
+            return _lowrank.fused_stack_inverse(list(self.flows), x, owner=self)
         log_det_jacobian_sum = 0
         for i, flow in reversed(list(enumerate(self.flows))):
             if self.batch_norm_between_layers and i < len(self.flows) - 1:

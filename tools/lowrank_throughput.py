@@ -15,8 +15,21 @@ hipEvent time of each of `--replays` calls after warm-up (median and min), and t
 bytes/s counted as B (2 dim + 1) 4 bytes: x in, z out, the log-det out. The parameters are redrawn
 at a contraction bound of 0.6 (tests/lowrank_cases.redraw): at the constructors' initialisation the
 layers are nearly the identity and the inverse stops at once. Prints one JSON line.
+
+    python tools/lowrank_throughput.py --train [--batch 1048576] [--layers 16] [--train-replays 3] [--out FILE.json]
+
+times one NLL step instead, `(-NormalizingFlowModel(layers).log_prob(x).mean()).backward()` with no
+optimizer, of the same two stacks on two routes of the same build, taken in turn:
+
+  fused      every layer with fused_backward = True: one forward launch that saves only its output, one
+             backward launch for the whole stack (csrc/nfx_lowrank_bwd*.hip), one parameter launch per layer
+  composite  the default: the forward kernels, then each layer's gradients recomputed through its torch
+             composite (autograd unrolled through the fixed-point loop)
+
+and reports every run, so "the fused step is faster in every run" can be read off.
 """
 import argparse
+import copy
 import json
 import os
 import statistics
@@ -57,6 +70,65 @@ def per_layer(flows, x, direction, bufs, ld):
     return cur, ld
 
 
+def step_ms(model, x):
+    """hipEvent milliseconds of one NLL step."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    model.zero_grad(set_to_none=True)
+    e0.record()
+    (-model.log_prob(x).mean()).backward()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def train(a, dev):
+    rows = []
+    B = a.batch
+    for name, dim, make in STACKS:
+        layers = [redraw(make(), 100 + i, 0.6).eval() for i in range(a.layers)]
+        plain = nfs_amd.NormalizingFlowModel([copy.deepcopy(f) for f in layers]).to(dev).eval()
+        fused = nfs_amd.NormalizingFlowModel([copy.deepcopy(f) for f in layers]).to(dev).eval()
+        for f in fused.flows:
+            f.fused_backward = True
+        x = (1.5 * torch.randn(B, dim, generator=torch.Generator().manual_seed(dim))).to(dev)
+        nfs_amd.reset_stats()
+        step_ms(fused, x)
+        assert nfs_amd.STATS["torch"] == 0, nfs_amd.STATS
+        nfs_amd.reset_stats()
+        step_ms(plain, x)
+        assert nfs_amd.STATS["torch"] == a.layers, nfs_amd.STATS
+        agree = max(float((p.grad - q.grad).abs().max() / q.grad.abs().max().clamp_min(1e-30))
+                    for p, q in zip(fused.parameters(), plain.parameters()))
+        ms, cms = [], []
+        for _ in range(a.train_replays):
+            ms.append(step_ms(fused, x))
+            cms.append(step_ms(plain, x))
+        plain.zero_grad(set_to_none=True)
+        torch.cuda.empty_cache()
+        rows.append({"stack": f"{a.layers} x {name}", "B": B, "fused_ms": ms, "composite_ms": cms,
+                     "fused_speedup_over_composite": statistics.median(cms) / statistics.median(ms),
+                     "fused_slowest_below_composite_fastest": max(ms) < min(cms),
+                     "max_relative_gradient_difference": agree})
+        print(f"[lowrank train] {a.layers} x {name} B={B}: fused " + " / ".join(f"{m:.3f}" for m in ms) + " ms, composite "
+              + " / ".join(f"{m:.1f}" for m in cms) + f" ms; fused is {statistics.median(cms) / statistics.median(ms):.0f}x; "
+              f"parameter gradients differ by {agree:.1e} relative (implicit against unrolled)", file=sys.stderr, flush=True)
+    return {"workload": "one NLL step: (-NormalizingFlowModel(layers).log_prob(x).mean()).backward(), no optimizer",
+            "device": torch.cuda.get_device_name(0), "runs": a.train_replays,
+            "all_below": all(r["fused_slowest_below_composite_fastest"] for r in rows), "results": rows}
+
+
+STACKS = (("PlanarFlow(16)", 16, lambda: nfs_amd.PlanarFlow(16)), ("SylvesterFlow(8)", 8, lambda: nfs_amd.SylvesterFlow(8)))
+
+
+def finish(res, out):
+    line = json.dumps(res)
+    print(line)
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1 << 20)
@@ -65,12 +137,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--eager-replays", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--train", action="store_true")
+    ap.add_argument("--train-replays", type=int, default=3)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.train:
+        res = train(a, dev)
+        finish(res, a.out)
+        return 0 if res["all_below"] else 1
     B = a.batch
     rows = []
-    for name, dim, make in (("PlanarFlow(16)", 16, lambda: nfs_amd.PlanarFlow(16)),
-                            ("SylvesterFlow(8)", 8, lambda: nfs_amd.SylvesterFlow(8))):
+    for name, dim, make in STACKS:
         flows = [redraw(make(), 100 + i, 0.6).to(dev).eval() for i in range(a.layers)]
         stack = nfs_amd.SequentialFlow(flows).eval()
         x = (1.5 * torch.randn(B, dim, generator=torch.Generator().manual_seed(dim))).to(dev)
@@ -109,13 +186,9 @@ def main():
                   f"differs from eager by {agree:.1e}", file=sys.stderr, flush=True)
     res = {"device": torch.cuda.get_device_name(0), "replays": a.replays, "eager_replays": a.eager_replays,
            "results": rows}
-    line = json.dumps(res)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(line + "\n")
+    finish(res, a.out)
+    return 0
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(main())
