@@ -756,6 +756,44 @@ int nfx_residual_flow(const float* packed, const float* in, float* out, float* l
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * ResidualFlow backward (eval-mode semantics, as above): the gradients of nfx_residual_flow's out
+ * and log_det with respect to its input and the six EFFECTIVE parameters, for 1 <= d <= 8 and
+ * 1 <= H <= 64 (nfx_residual_backward_supported: 1 inside the family, host-only; H > 64 is outside
+ * it). Straight-through: the gradient of an effective weight is returned as the parameter's, with no
+ * sigma term; u and v get none.
+ *   nfx_residual_pack_backward  the arguments of nfx_residual_pack; writes the backward's image,
+ *                               nfx_residual_backward_packed_floats floats. It BEGINS with the forward
+ *                               image, bit for bit, so the same buffer serves nfx_residual_flow.
+ *   nfx_residual_backward       gx [B, d] and gw1 [H, d], gb1 [H], gw2 [H, H], gb2 [H], gw3 [d, H],
+ *                               gb3 [d] (overwritten, not accumulated) from the cotangents gy [B, d]
+ *                               and gld [B] of (out, log_det) and the point z [B, d]: the call's INPUT
+ *                               for NFX_FORWARD, its OUTPUT for NFX_INVERSE. The inverse's gradient is
+ *                               the implicit-function one at z (one d x d solve of (I + J)^T per
+ *                               sample, LU with partial pivoting), not the unrolled iteration's.
+ *                               workspace: nfx_residual_backward_workspace_floats floats, anything on
+ *                               entry. Three launches: the main kernel (one wave per 32-row tile up to
+ *                               nfx_residual_backward_slots waves, nfx_residual_backward_block_threads
+ *                               threads per workgroup; each wave leaves its partial sums in its own
+ *                               workspace slot), the slot reduction in index order in float64, and the
+ *                               finish. No atomics: the same call twice gives the same bits.
+ * A row whose z, cotangents, Jacobian or solve holds a non-finite value (a zero pivot counts) adds
+ * nothing to any parameter gradient and gets gx = 0. neumann_terms = 0: log_det takes no part.
+ * gx must not alias gy or z. B == 0 is a no-op.
+ * ------------------------------------------------------------------------------------- */
+int nfx_residual_backward_supported(int64_t B, int d, int H, int activation);
+size_t nfx_residual_backward_packed_floats(int d, int H);
+size_t nfx_residual_backward_workspace_floats(int64_t B, int d, int H);
+size_t nfx_residual_backward_slots(int64_t B, int d, int H);
+size_t nfx_residual_backward_block_threads(int64_t B, int d, int H);
+int nfx_residual_pack_backward(const float* w1, const float* b1, const float* u1, const float* v1, float c1,
+                               const float* w2, const float* b2, const float* u2, const float* v2, float c2,
+                               const float* w3, const float* b3, const float* u3, const float* v3, float c3, int d,
+                               int H, float* packed, void* stream);
+int nfx_residual_backward(const float* packed, const float* z, const float* gy, const float* gld, float* gx,
+                          float* gw1, float* gb1, float* gw2, float* gb2, float* gw3, float* gb3, float* workspace,
+                          int64_t B, int d, int H, int activation, int direction, int neumann_terms, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * NeuralAutoregressiveFlow (src/flows/advanced/neural_autoregressive_flow.py): an affine
  * autoregressive flow on the DeepMADE conditioner,
  *   h_0 = act(LN(W_0 x + b_0)),  h_l = act(LN(W_l h_(l-1) + b_l)) [+ h_(l-1) in a residual block],

@@ -13,12 +13,13 @@
 //     tiles fit the register file; each group recomputes the value chain for g2);
 //   * the Neumann traces with the d x d powers in registers;
 //   * the fixed-point iteration inside the kernel, with a per-sample stopping rule (include/nfx.h);
-//   * the spectral normalisation at pack time, on the device (residual_pack_kernel).
+//   * the spectral normalisation at pack time, on the device (residual_pack_kernel); the same
+//     kernel writes the backward's image (nfx_residual_bwd.hip), which begins with this one.
 // The activation is a launch-uniform switch taken once per accumulator tile, not a template
 // parameter: 24 instantiations (3 padded widths x 8 dims) instead of 96.
 #include <math.h>
 
-#include "nfx_residual_kernel.h"
+#include "nfx_residual_bwd_kernel.h"
 
 namespace nfx {
 
@@ -37,6 +38,7 @@ struct ResLayerRaw {
 struct ResPackArgs {
     ResLayerRaw layer[3];
     int d, H;
+    int total;  // the forward image, or the backward's (res_bwd_layout) that begins with it
     float* packed;
 };
 
@@ -87,7 +89,7 @@ __global__ __launch_bounds__(kResPackThreads) void residual_pack_kernel(ResPackA
     const int HT = hidden_tiles(H);
     const ResLayout L = res_layout(d, HT);
     const float *w1 = P.layer[0].w, *w2 = P.layer[1].w, *w3 = P.layer[2].w;
-    for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < L.total; o += gridDim.x * blockDim.x) {
+    for (int o = blockIdx.x * blockDim.x + threadIdx.x; o < P.total; o += gridDim.x * blockDim.x) {
         float v = 0.f;
         if (o < L.b1) {  // w1: layer-1 A operand
             const RowCol e = a1_elem(o - L.w1, L.KS1);
@@ -105,12 +107,32 @@ __global__ __launch_bounds__(kResPackThreads) void residual_pack_kernel(ResPackA
         } else if (o < L.w2) {  // b3
             const int j = o - L.b3;
             if (j < d) v = P.layer[2].b[j];
-        } else {  // w2: A operand over (out row k, hidden input j)
+        } else if (o < L.total) {  // w2: A operand over (out row k, hidden input j)
             const RowCol e = a_image_elem(o - L.w2, HT);
             if (e.row < H && e.col < H) v = w2[e.row * H + e.col] * sc[1];
+        } else if (o < L.total + HT * HT * 1024) {  // w2t (backward image): A operand of W2^T
+            const RowCol e = a_image_elem(o - L.total, HT);
+            if (e.row < H && e.col < H) v = w2[e.col * H + e.row] * sc[1];
         }
         P.packed[o] = v;
     }
+}
+
+int residual_pack_launch(const float* const (&w)[3], const float* const (&b)[3], const float* const (&u)[3],
+                         const float* const (&v)[3], const float (&c)[3], int d, int H, float* packed, bool backward,
+                         hipStream_t stream) {
+    ResPackArgs P{};
+    P.layer[0] = ResLayerRaw{w[0], b[0], u[0], v[0], c[0], H, d};
+    P.layer[1] = ResLayerRaw{w[1], b[1], u[1], v[1], c[1], H, H};
+    P.layer[2] = ResLayerRaw{w[2], b[2], u[2], v[2], c[2], d, H};
+    P.d = d;
+    P.H = H;
+    const int HT = hidden_tiles(H);
+    P.total = backward ? res_bwd_layout(d, HT).total : res_layout(d, HT).total;
+    P.packed = packed;
+    const int per_block = 4 * kResPackThreads;
+    residual_pack_kernel<<<(P.total + per_block - 1) / per_block, kResPackThreads, 0, stream>>>(P);
+    return check_launch("residual_pack_kernel");
 }
 
 }  // namespace nfx
@@ -134,17 +156,8 @@ extern "C" int nfx_residual_pack(const float* w1, const float* b1, const float* 
     if (!res_family(d, H))
         return set_error(NFX_EUNSUPPORTED, "residual: d=%d H=%d outside the compiled family (d<=8, H<=128)", d, H);
     if (int rc = check_pointers("residual_pack", {w1, b1, u1, v1, w2, b2, u2, v2, w3, b3, u3, v3, packed})) return rc;
-    ResPackArgs P{};
-    P.layer[0] = ResLayerRaw{w1, b1, u1, v1, c1, H, d};
-    P.layer[1] = ResLayerRaw{w2, b2, u2, v2, c2, H, H};
-    P.layer[2] = ResLayerRaw{w3, b3, u3, v3, c3, d, H};
-    P.d = d;
-    P.H = H;
-    P.packed = packed;
-    const int total = (int)nfx_residual_packed_floats(d, H);
-    const int per_block = 4 * kResPackThreads;
-    residual_pack_kernel<<<(total + per_block - 1) / per_block, kResPackThreads, 0, (hipStream_t)stream>>>(P);
-    return check_launch("residual_pack_kernel");
+    return residual_pack_launch({w1, w2, w3}, {b1, b2, b3}, {u1, u2, u3}, {v1, v2, v3}, {c1, c2, c3}, d, H, packed, false,
+                                (hipStream_t)stream);
 }
 
 extern "C" int nfx_residual_flow(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,

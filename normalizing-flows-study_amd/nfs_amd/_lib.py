@@ -181,6 +181,13 @@ _SIGNATURES = {
     "nfx_residual_supported": (_int, [_i64, _int, _int, _int]),
     "nfx_residual_pack": (_int, [_vp, _vp, _vp, _vp, _f] * 3 + [_int, _int, _vp, _vp]),
     "nfx_residual_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _f, _int, _vp]),
+    "nfx_residual_backward_supported": (_int, [_i64, _int, _int, _int]),
+    "nfx_residual_backward_packed_floats": (_sz, [_int, _int]),
+    "nfx_residual_backward_workspace_floats": (_sz, [_i64, _int, _int]),
+    "nfx_residual_backward_slots": (_sz, [_i64, _int, _int]),
+    "nfx_residual_backward_block_threads": (_sz, [_i64, _int, _int]),
+    "nfx_residual_pack_backward": (_int, [_vp, _vp, _vp, _vp, _f] * 3 + [_int, _int, _vp, _vp]),
+    "nfx_residual_backward": (_int, [_vp] * 12 + [_i64, _int, _int, _int, _int, _int, _vp]),
     "nfx_naf_packed_floats": (_sz, [_int, _int, _vp]),
     "nfx_naf_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
     "nfx_naf_pack": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
@@ -275,7 +282,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
     "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
-    "nfx_made_sample_supported", "nfx_residual_supported", "nfx_naf_supported", "nfx_naf_backward_supported",
+    "nfx_made_sample_supported", "nfx_residual_supported", "nfx_residual_backward_supported",
+    "nfx_naf_supported", "nfx_naf_backward_supported",
     "nfx_lowrank_supported", "nfx_lrbwd_supported"))
 
 

@@ -31,7 +31,18 @@ TWO DELIBERATE DIFFERENCES from the reference:
   * Train mode always runs the composite (`_torch_only`): its semantics mutate buffers inside one
     call. The gfx950 kernel (csrc/nfx_residual*.hip, one launch per call) is for eval mode, dim <= 8
     and hidden_dim <= 128; other shapes raise NotImplementedError on the GPU (or run the composite
-    with ALLOW_TORCH_FALLBACK). Gradients in eval mode recompute through the composite.
+    with ALLOW_TORCH_FALLBACK).
+
+Gradients in eval mode recompute through the composite by default. With
+`ResidualFlow.fused_backward = True` (on the class or an instance) they come from the fused backward
+kernels (csrc/nfx_residual_bwd*.hip) for dim <= 8 and hidden_dim <= 64, in HIP only: the unchanged
+forward kernel, then one main kernel, a fixed-order float64 reduction and a finish. hidden_dim 65..128
+and train mode keep the composite route. A THIRD DELIBERATE DIFFERENCE, on that route only: the
+inverse's gradient is the implicit-function gradient at the returned z (one dim x dim solve of
+(I + J)^T per sample), not the gradient of the unrolled iteration the composite differentiates; the
+two differ by the iteration's residual (README). A row with a non-finite value adds nothing to the
+parameter gradients and gets a zero input gradient, where autograd gives NaN. Double backward is not
+supported there.
 """
 import torch
 import torch.nn as nn
@@ -185,8 +196,12 @@ class ResidualBlock(nn.Module):
 
 
 class ResidualFlow(HipFlow):
-    """Residual flow (residual_flow.py:153-340); see the module docstring for the two deliberate
+    """Residual flow (residual_flow.py:153-340); see the module docstring for the deliberate
     differences from the reference."""
+
+    # True: eval-mode gradients come from the fused backward kernels (csrc/nfx_residual_bwd*.hip) for
+    # dim <= 8 and hidden_dim <= 64; False (the default) recomputes through the composite on the GPU.
+    fused_backward = False
 
     def __init__(self, dim, hidden_dim=64, lipschitz_constant=0.9, activation="relu", max_iter=100, tol=1e-6,
                  neumann_terms=3):
@@ -276,12 +291,7 @@ class ResidualFlow(HipFlow):
         L = _lib.checked()
         d, H = self.dim, self.residual_block.layer1.module.out_features
         packed = torch.empty(L.nfx_residual_packed_floats(d, H), device=device, dtype=torch.float32)
-        args = []
-        for l in self.residual_block.layers():
-            args += [_lib.dense(t.detach().to(device=device, dtype=torch.float32))
-                     for t in (l.module.weight, l.module.bias, l.u, l.v)]
-            args.append(float(l.lipschitz_constant))
-        L.nfx_residual_pack(*args, d, H, packed, _lib.stream_of(packed))
+        L.nfx_residual_pack(*self._raw_layers(device), d, H, packed, _lib.stream_of(packed))
         return packed
 
     def _hip_launch(self, x, out, log_det, direction, accumulate):
@@ -291,3 +301,80 @@ class ResidualFlow(HipFlow):
             packed, x, out, log_det, x.shape[0], self.dim, block.layer1.module.out_features, block.activation_code(),
             _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE, int(self.neumann_terms), int(self.max_iter),
             float(self.tol), int(bool(accumulate)), _lib.stream_of(x))
+
+    # -- fused backward (opt-in: ResidualFlow.fused_backward = True) -------------------------------
+    def _dispatch(self, x, direction):
+        if (self.fused_backward and torch.is_grad_enabled() and self._route(x) == "hip"
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+                and self._hip_backward_ok(x, direction)):
+            return _ResidualFunction.apply(self, direction, x, *list(self.parameters()))
+        return super()._dispatch(x, direction)
+
+    def _hip_backward_ok(self, x, direction):
+        """The fused backward is switched on and has kernels for this shape (dim <= 8, hidden_dim
+        <= 64); otherwise the gradients recompute through the composite."""
+        block = self.residual_block
+        return bool(self.fused_backward and x.dim() == 2 and x.shape[1] == self.dim and x.shape[0] >= 1
+                    and _lib.lib().nfx_residual_backward_supported(
+                        x.shape[0], self.dim, block.layer1.module.out_features, block.activation_code()))
+
+    def _raw_layers(self, device):
+        """nfx_residual_pack's leading arguments: (weight, bias, u, v, c) per layer."""
+        args = []
+        for l in self.residual_block.layers():
+            args += [_lib.dense(t.detach().to(device=device, dtype=torch.float32))
+                     for t in (l.module.weight, l.module.bias, l.u, l.v)]
+            args.append(float(l.lipschitz_constant))
+        return args
+
+    def _build_backward_pack(self, device):
+        L = _lib.checked()
+        d, H = self.dim, self.residual_block.layer1.module.out_features
+        packed = torch.empty(L.nfx_residual_backward_packed_floats(d, H), device=device, dtype=torch.float32)
+        L.nfx_residual_pack_backward(*self._raw_layers(device), d, H, packed, _lib.stream_of(packed))
+        return packed
+
+    def _hip_backward(self, z, gy, gld, direction):
+        """(gx, [gW1, gb1, gW2, gb2, gW3, gb3]) in HIP only. `z` is the point the layer's function is
+        differentiated at: the call's input (forward) or its output (inverse)."""
+        L = _lib.checked()
+        z = _lib.dense(z)
+        block = self.residual_block
+        B, d, H = z.shape[0], self.dim, block.layer1.module.out_features
+        packed = self._packed(z.device, self._build_backward_pack, slot="_nfx_bwd_pack_cache")
+        gy = _lib.dense(gy.to(torch.float32))
+        gld = _lib.dense(gld.to(torch.float32))
+        gx = torch.empty_like(z)
+        grads = [torch.empty(p.shape, device=z.device, dtype=torch.float32)
+                 for l in block.layers() for p in (l.module.weight, l.module.bias)]
+        ws = torch.empty(L.nfx_residual_backward_workspace_floats(B, d, H), device=z.device, dtype=torch.float32)
+        L.nfx_residual_backward(packed, z, gy, gld, gx, *grads, ws, B, d, H, block.activation_code(),
+                                _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE, int(self.neumann_terms),
+                                _lib.stream_of(z))
+        return gx, grads
+
+
+class _ResidualFunction(torch.autograd.Function):
+    """Eval-mode ResidualFlow with the fused backward: the unchanged forward kernel, then the backward
+    kernels. It keeps the point of differentiation: the input (forward) or the output z (inverse).
+    No composite anywhere; double backward is not supported."""
+
+    @staticmethod
+    def forward(ctx, layer, direction, x, *params):
+        x = _lib.dense(x)
+        with torch.no_grad():
+            y, ld = layer._hip_call(x.detach(), direction)
+        ctx.layer, ctx.direction = layer, direction
+        ctx.save_for_backward(x if direction > 0 else y)
+        return y, ld
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy, gld):
+        from . import flow as _flow
+        (z,) = ctx.saved_tensors
+        layer = ctx.layer
+        _flow.STATS["hip"] += 1
+        gx, gparams = layer._hip_backward(z.detach(), gy, gld, ctx.direction)
+        gparams = [g if p.requires_grad else None for p, g in zip(layer.parameters(), gparams)]
+        return (None, None, gx, *gparams)
