@@ -842,6 +842,26 @@ int nfx_naf_flow(const float* packed, const float* in, float* out, float* log_de
                  const int* widths, int activation, int flags, float clamp_alpha, float clamp_log_scale,
                  int direction, int accumulate, void* stream);
 
+/* The wide kernel family of the same flow: 1 <= d <= 16, 1 <= n_hidden <= 4, every width in 1..512
+ * (the constructor's default [512, 512, 512] among them), all four activations, LayerNorm on or off,
+ * residual blocks; any B >= 1. Arguments, semantics, flags, return codes and the image
+ * (nfx_naf_wide_packed_floats floats, written by nfx_naf_wide_pack) are those of the functions above;
+ * an image packed by either pack function serves either flow function. The kernel differs: a
+ * four-wave workgroup owns each 32-row tile, a layer's activations sit in LDS (two buffers of up to
+ * 64 KiB), and the image stays in global memory and streams through L2, so neither a width nor the
+ * image is bound by LDS or the register file. One launch (naf_wide_kernel) per call and direction,
+ * stream-ordered, no allocation. The family contains the narrow one; a caller that wants the
+ * LDS-resident kernel where it exists asks nfx_naf_supported first (the Python layer does, under
+ * NeuralAutoregressiveFlow.wide_kernel = True). Forward values only: nfx_naf_backward keeps its
+ * own family (widths up to 64), and no backward exists for wider layers. */
+size_t nfx_naf_wide_packed_floats(int d, int n_hidden, const int* widths);
+int nfx_naf_wide_supported(int64_t B, int d, int n_hidden, const int* widths, int activation, int flags);
+int nfx_naf_wide_pack(const NfxNafLayer* layers, int d, int n_hidden, const int* widths, float* packed,
+                      void* stream);
+int nfx_naf_wide_flow(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,
+                      int n_hidden, const int* widths, int activation, int flags, float clamp_alpha,
+                      float clamp_log_scale, int direction, int accumulate, void* stream);
+
 /* Backward of NFX_INVERSE (the density direction, the one an NLL step uses): the gradients autograd
  * gives for the composite, of <gz, out> + <gld, log_det>, with respect to the input and every
  * parameter. The conditioner is recomputed from x inside the kernel, so the forward saves nothing.

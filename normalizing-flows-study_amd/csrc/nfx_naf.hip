@@ -122,22 +122,18 @@ extern "C" int nfx_naf_supported(int64_t B, int d, int n_hidden, const int* widt
                : 0;
 }
 
-extern "C" int nfx_naf_pack(const NfxNafLayer* layers, int d, int n_hidden, const int* widths, float* packed,
-                            void* stream) {
-    if (d <= 0 || n_hidden <= 0 || !widths)
-        return set_error(NFX_EINVAL, "naf_pack: bad shape d=%d n_hidden=%d", d, n_hidden);
-    if (const char* why = naf_shape_problem(d, n_hidden, widths))
-        return set_error(NFX_EUNSUPPORTED, "naf: d=%d n_hidden=%d %s (%s)", d, n_hidden, kNafFamily, why);
-    if (int rc = check_pointers("naf_pack", {layers, packed})) return rc;
+int nfx::naf_pack_image(const char* who, const NfxNafLayer* layers, int d, int n_hidden, const int* widths,
+                        float* packed, hipStream_t stream) {
+    if (int rc = check_pointers(who, {layers, packed})) return rc;
     NafPackArgs P{};
     for (int l = 0; l <= n_hidden; ++l) {
         const NfxNafLayer& r = layers[l];
-        if (!r.weight || !r.bias) return set_error(NFX_EINVAL, "naf_pack: layer %d weight or bias is null", l);
+        if (!r.weight || !r.bias) return set_error(NFX_EINVAL, "%s: layer %d weight or bias is null", who, l);
         if ((r.ln_weight == nullptr) != (r.ln_bias == nullptr))
-            return set_error(NFX_EINVAL, "naf_pack: layer %d needs both LayerNorm vectors or neither", l);
+            return set_error(NFX_EINVAL, "%s: layer %d needs both LayerNorm vectors or neither", who, l);
         if (r.residual && (l < 1 || l >= n_hidden || widths[l] != widths[l - 1]))
-            return set_error(NFX_EINVAL, "naf_pack: layer %d cannot be a residual block", l);
-        if (l == n_hidden && r.ln_weight) return set_error(NFX_EINVAL, "naf_pack: the output layer has no LayerNorm");
+            return set_error(NFX_EINVAL, "%s: layer %d cannot be a residual block", who, l);
+        if (l == n_hidden && r.ln_weight) return set_error(NFX_EINVAL, "%s: the output layer has no LayerNorm", who);
         P.raw[l] = r;
     }
     P.lay = naf_layout(d, n_hidden, widths);
@@ -145,8 +141,17 @@ extern "C" int nfx_naf_pack(const NfxNafLayer* layers, int d, int n_hidden, cons
     P.nh = n_hidden;
     P.packed = packed;
     const int per_block = 4 * kNafPackThreads;
-    naf_pack_kernel<<<(P.lay.total + per_block - 1) / per_block, kNafPackThreads, 0, (hipStream_t)stream>>>(P);
+    naf_pack_kernel<<<(P.lay.total + per_block - 1) / per_block, kNafPackThreads, 0, stream>>>(P);
     return check_launch("naf_pack_kernel");
+}
+
+extern "C" int nfx_naf_pack(const NfxNafLayer* layers, int d, int n_hidden, const int* widths, float* packed,
+                            void* stream) {
+    if (d <= 0 || n_hidden <= 0 || !widths)
+        return set_error(NFX_EINVAL, "naf_pack: bad shape d=%d n_hidden=%d", d, n_hidden);
+    if (const char* why = naf_shape_problem(d, n_hidden, widths))
+        return set_error(NFX_EUNSUPPORTED, "naf: d=%d n_hidden=%d %s (%s)", d, n_hidden, kNafFamily, why);
+    return naf_pack_image("naf_pack", layers, d, n_hidden, widths, packed, (hipStream_t)stream);
 }
 
 extern "C" int nfx_naf_flow(const float* packed, const float* in, float* out, float* log_det, int64_t B, int d,

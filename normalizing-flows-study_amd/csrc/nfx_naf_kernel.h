@@ -354,4 +354,9 @@ naf_kernel_t naf_pick_ht<2>();
 template <>
 naf_kernel_t naf_pick_ht<4>();
 
+// Launch the pack kernel of the image (nfx_naf.hip), for a shape the caller has checked: both kernel
+// families read the same image. `who` names the entry point in the error text.
+int naf_pack_image(const char* who, const NfxNafLayer* layers, int d, int n_hidden, const int* widths, float* packed,
+                   hipStream_t stream);
+
 }  // namespace nfx

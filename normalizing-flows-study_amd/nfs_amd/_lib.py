@@ -192,6 +192,10 @@ _SIGNATURES = {
     "nfx_naf_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
     "nfx_naf_pack": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
     "nfx_naf_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _f, _f, _int, _int, _vp]),
+    "nfx_naf_wide_packed_floats": (_sz, [_int, _int, _vp]),
+    "nfx_naf_wide_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
+    "nfx_naf_wide_pack": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
+    "nfx_naf_wide_flow": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _f, _f, _int, _int, _vp]),
     "nfx_naf_backward_supported": (_int, [_i64, _int, _int, _vp, _int, _int]),
     "nfx_naf_backward_packed_floats": (_sz, [_int, _int, _vp]),
     "nfx_naf_pack_backward": (_int, [_vp, _int, _int, _vp, _vp, _vp]),
@@ -283,7 +287,7 @@ _VALUE_RETURNING = frozenset((
     "nfx_abi_version", "nfx_affine_kernel_policy", "nfx_made_seq_policy", "nfx_affine_chain_supported",
     "nfx_spline_chain_supported", "nfx_cnf_supported", "nfx_cnf_backward_supported",
     "nfx_made_sample_supported", "nfx_residual_supported", "nfx_residual_backward_supported",
-    "nfx_naf_supported", "nfx_naf_backward_supported",
+    "nfx_naf_supported", "nfx_naf_wide_supported", "nfx_naf_backward_supported",
     "nfx_lowrank_supported", "nfx_lrbwd_supported"))
 
 

@@ -35,6 +35,14 @@ where autograd on the composite gives NaN (0 * NaN behind torch.where). The kern
 whose packed image fits the LDS of one workgroup (nfx_naf_supported decides), relu / elu /
 leaky_relu(0.1) / gelu; the constructor's default [512, 512, 512] is outside it and raises
 NotImplementedError on the GPU (or runs the composite with ALLOW_TORCH_FALLBACK).
+
+With `NeuralAutoregressiveFlow.wide_kernel = True` (on the class or an instance; off by default, so
+that a shape that raised keeps raising) a shape outside that family runs the wide kernel
+(csrc/nfx_naf_wide*.hip) when it lies in the wide family: the same dims, layer counts and activations
+with widths up to 512, activations in LDS and the weights streamed from global memory, one launch per
+call and direction. A shape inside the narrow family takes the narrow kernel whatever the switch
+says, with the same bits. The wide family has no fused backward: its gradients recompute through the
+composite, and train mode with dropout > 0 runs the composite, as everywhere.
 """
 import ctypes
 
@@ -48,6 +56,8 @@ from .flow import HipFlow
 
 _FAMILY = ("the kernel family (1 <= dim <= 16, 1 to 4 hidden layers of width 1..128 with the packed image inside "
            "160 KiB of LDS, relu / elu / leaky_relu(0.1) / gelu, the network the constructor builds)")
+_WIDE_FAMILY = ("the wide kernel family (wide_kernel = True: 1 <= dim <= 16, 1 to 4 hidden layers of width 1..512, "
+                "the same activations)")
 
 
 def activation_code(a):
@@ -229,6 +239,10 @@ class NeuralAutoregressiveFlow(HipFlow):
     # True: the gradients of `inverse` come from the fused backward kernels (csrc/nfx_naf_bwd*.hip) for
     # 1 to 4 hidden layers of width 1..64; False (the default) recomputes through the composite on the GPU.
     fused_backward = False
+    # True: a shape outside the narrow kernel family (nfx_naf_supported) runs the wide kernel
+    # (csrc/nfx_naf_wide*.hip; widths up to 512, the default constructor's among them) instead of
+    # raising NotImplementedError. Shapes inside the narrow family are not affected.
+    wide_kernel = False
 
     def __init__(self, dim, hidden_dims=[512, 512, 512], activation="relu", use_layer_norm=True, use_residual=True,
                  dropout=0.1, clamp_alpha=3.0, clamp_log_scale=5.0):
@@ -327,33 +341,58 @@ class NeuralAutoregressiveFlow(HipFlow):
         # (the activation is read at every call: an attribute of the shared module may change in place)
         code = activation_code(hidden[0][2])
         keep, widths_ptr = self._widths_arg(plan)
-        if not _lib.checked().nfx_naf_supported(max(x.shape[0], 1), self.dim, len(hidden), widths_ptr, code, flags):
-            return False, (f"dim={self.dim} hidden_dims={list(widths)} activation={type(hidden[0][2]).__name__} "
-                           f"outside {_FAMILY}")
-        return True, ""
+        L = _lib.checked()
+        B = max(x.shape[0], 1)
+        if L.nfx_naf_supported(B, self.dim, len(hidden), widths_ptr, code, flags):
+            return True, ""
+        outside = _FAMILY
+        if self.wide_kernel:
+            if L.nfx_naf_wide_supported(B, self.dim, len(hidden), widths_ptr, code, flags):
+                return True, ""
+            outside = f"{_FAMILY} and outside {_WIDE_FAMILY}"
+        return False, (f"dim={self.dim} hidden_dims={list(widths)} activation={type(hidden[0][2]).__name__} "
+                       f"outside {outside}")
+
+    def _wide(self):
+        """The call runs the wide kernel: the switch is on and the narrow family does not hold the
+        shape (asked at every call, like the activation: both may change in place)."""
+        if not self.wide_kernel:
+            return False
+        plan = self._plan()
+        keep, widths_ptr = self._widths_arg(plan)
+        return not _lib.checked().nfx_naf_supported(1, self.dim, len(plan[0]), widths_ptr,
+                                                    activation_code(plan[0][0][2]), plan[4])
 
     def _state_key(self, device):
         plan = self._plan()
         eps = () if plan is None else tuple(None if ln is None else ln.eps for _, ln, _, _ in plan[0])
         return super()._state_key(device) + eps
 
-    def _build_pack(self, device):
+    def _build_pack(self, device, wide=False):
         L = _lib.checked()
         plan = self._plan()
         hidden = plan[0]
         widths, widths_ptr = self._widths_arg(plan)
         raw, keep = self._raw_layers(device)
-        packed = torch.empty(L.nfx_naf_packed_floats(self.dim, len(hidden), widths_ptr), device=device,
-                             dtype=torch.float32)
-        L.nfx_naf_pack(ctypes.addressof(raw), self.dim, len(hidden), widths_ptr, packed, _lib.stream_of(packed))
+        floats, pack = (L.nfx_naf_wide_packed_floats, L.nfx_naf_wide_pack) if wide else \
+            (L.nfx_naf_packed_floats, L.nfx_naf_pack)
+        packed = torch.empty(floats(self.dim, len(hidden), widths_ptr), device=device, dtype=torch.float32)
+        pack(ctypes.addressof(raw), self.dim, len(hidden), widths_ptr, packed, _lib.stream_of(packed))
         return packed
 
+    def _build_wide_pack(self, device):
+        return self._build_pack(device, wide=True)
+
     def _hip_launch(self, x, out, log_det, direction, accumulate):
-        packed = self._packed(x.device, self._build_pack)
+        # (one cache slot per family: toggling the switch never hands a kernel the other's image)
+        wide = self._wide()
+        packed = self._packed(x.device, self._build_wide_pack, slot="_nfx_wide_pack_cache") if wide else \
+            self._packed(x.device, self._build_pack)
         plan = self._plan()
         hidden, flags = plan[0], plan[4]
         widths, widths_ptr = self._widths_arg(plan)
-        _lib.checked().nfx_naf_flow(
+        L = _lib.checked()
+        (L.nfx_naf_wide_flow if wide else L.nfx_naf_flow)(
             packed, x, out, log_det, x.shape[0], self.dim, len(hidden), widths_ptr, activation_code(hidden[0][2]), flags,
             float(self.clamp_alpha), float(self.clamp_log_scale),
             _lib.NFX_FORWARD if direction > 0 else _lib.NFX_INVERSE, int(bool(accumulate)), _lib.stream_of(x))

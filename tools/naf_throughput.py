@@ -25,6 +25,16 @@ the optimizer left out, for (4, [64, 64]) and (16, [64, 64]): the fused backward
 route (the flag off: the fused forward kernel, then the eager DeepMADE and autograd), the same windows
 taken in turn, `--calls` steps per window on both routes. The fused step's slowest window must lie
 below the composite route's fastest in every cell (`all_below`, and the exit status).
+
+    python tools/naf_throughput.py --wide [--batches 1024,65536] [--replays 20] [--calls 50] [--out FILE.json]
+
+`--wide` times the wide kernel family (`wide_kernel = True`, csrc/nfx_naf_wide*.hip) on the constructor's
+default widths, (2, [512, 512, 512]) and (16, [512, 512, 512]), by the same method against the same
+comparator. Every window is kept in the result (`fused_ms_windows`, `eager_ms_windows`). A cell holds
+when the fused call's slowest window lies below the eager composite's fastest (`all_below`, and the
+exit status). `mfma_tflops_from_call_time` is the fp32 MFMA work the kernel executes (padded tiles,
+every pass, 4,096 flop per v_mfma_f32_32x32x2_f32) divided by the median time per CALL, so it
+understates what the matrix pipe reaches inside the kernel.
 """
 import argparse
 import copy
@@ -41,6 +51,16 @@ sys.path.insert(0, os.path.join(ROOT, "normalizing-flows-study_amd"))
 import nfs_amd  # noqa: E402
 
 MODELS = [(4, [64, 64]), (16, [128, 128])]
+WIDE_MODELS = [(2, [512, 512, 512]), (16, [512, 512, 512])]
+
+
+def wide_mfma_flop(d, hidden, B, direction):
+    """fp32 MFMA flop one wide-kernel call executes: per 32-row tile and conditioner pass, 4 (d <= 8) or
+    8 k-steps per out tile of the first layer and 16 per (out tile, k tile) pair above it, the output
+    layer being one out tile; one pass for the inverse, d for the forward."""
+    nt = [(w + 31) // 32 for w in hidden]
+    mfma = nt[0] * (4 if d <= 8 else 8) + sum(16 * a * b for a, b in zip(nt[1:], nt[:-1])) + 16 * nt[-1]
+    return 4096 * mfma * ((B + 31) // 32) * (d if direction == "forward" else 1)
 
 
 def make_flow(d, hidden, activation, device):
@@ -143,14 +163,17 @@ def main():
     ap.add_argument("--activation", default="relu")
     ap.add_argument("--out", default=None)
     ap.add_argument("--train", action="store_true")
+    ap.add_argument("--wide", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.train:
         res, ok = train(a, dev)
         return finish(res, ok, a.out)
     rows = []
-    for d, hidden in MODELS:
+    models = WIDE_MODELS if a.wide else MODELS
+    for d, hidden in models:
         flow = make_flow(d, hidden, a.activation, dev)
+        flow.wide_kernel = a.wide
         eager = copy.deepcopy(flow)
         eager._torch_only = lambda: True  # every call takes the torch composite route
         for B in [int(b) for b in a.batches.split(",")]:
@@ -171,13 +194,20 @@ def main():
                              "eager_ms_min": min(ems), "eager_ms_max": max(ems),
                              "eager_samples_per_s": B / (emed * 1e-3), "fused_speedup_over_eager": emed / med,
                              "fused_is_faster": med < emed, "max_abs_difference": agree})
+                if a.wide:
+                    rows[-1].update({"fused_slowest_below_eager_fastest": max(ms) < min(ems),
+                                     "mfma_tflops_from_call_time": wide_mfma_flop(d, hidden, B, name) / (med * 1e9),
+                                     "fused_ms_windows": ms, "eager_ms_windows": ems})
                 print(f"[naf] ({d}, {hidden}) B={B} {name}: fused {med:.3f} ms (min {min(ms):.3f}, max {max(ms):.3f}), "
                       f"eager composite {emed:.3f} ms (min {min(ems):.3f}, max {max(ems):.3f}); fused is "
                       f"{emed / med:.1f}x; outputs differ by {agree:.1e}", file=sys.stderr, flush=True)
-    res = {"models": [f"NeuralAutoregressiveFlow({d}, {h}, activation={a.activation!r})" for d, h in MODELS],
+    res = {"models": [f"NeuralAutoregressiveFlow({d}, {h}, activation={a.activation!r})" for d, h in models],
            "device": torch.cuda.get_device_name(0), "replays": a.replays, "calls_per_window": a.calls,
            "eager_calls_per_window": a.eager_calls,
            "all_faster": all(r["fused_ms_median"] < r["eager_ms_median"] for r in rows), "results": rows}
+    if a.wide:
+        res["all_below"] = all(r["fused_slowest_below_eager_fastest"] for r in rows)
+        return finish(res, res["all_below"], a.out)
     return finish(res, res["all_faster"], a.out)
 
 
